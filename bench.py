@@ -33,12 +33,21 @@ the timing barrier and the max-over-ranks reduction are the only RCCL calls
 Reports (one JSON line on rank 0): value = channel-samples/s over all ranks,
 the roofline of the dominant kernel (HIP events on the launch stream, inside
 the timed region) and of the whole step (roofline.pipeline_frac: algorithmic
-bytes of every kernel of a step / ms_per_step / 8 TB/s), and the CPU oracle
-timed on a bounded channel sample; next
+bytes of every kernel of a step / ms_per_step / 8 TB/s); next
 to them the first and steady step spans (step_ms_first / step_ms_steady: the
-first timed step starts on an idle GPU and carries its host planning) and the
-GPU's socket power and gfx clock through the timed steps (gpu_power).
+first timed step starts on an idle GPU and carries its host planning).
 Defaults: 20 timed steps after 2 warm-up steps, N = 1.
+
+A plain run does only that: set up, warm up, time the steps, print the line.
+--full adds the measurements that take time of their own: the CPU oracle timed
+on a bounded channel sample (one core and all-core), the GPU's socket power
+and gfx clock through the timed steps (gpu_power), and for the tutorial
+workloads the published stage alone next to the oracle on the same shape.
+
+--dump-outputs DIR writes what the last timed step returned to its caller
+(signal.data of this rank) as DIR/data.npy, float32: the whole array when it
+is small, else a fixed seeded sample of its rows and columns.  The engine is
+seeded, so the same arguments give the same data on every run.
 """
 import argparse
 import contextlib
@@ -425,6 +434,28 @@ def cpu_model():
     return platform.processor()
 
 
+DUMP_WHOLE_BYTES = 32 << 20     # outputs up to this size are written whole
+DUMP_ROWS, DUMP_COLS = 64, 1 << 16
+
+
+def dump_outputs(dirname, sig, rank, world):
+    """--dump-outputs: the step's product (signal.data, this rank's channels)
+    as float32 in DIR/data.npy (data_rank<r>.npy when there are several
+    ranks).  A larger array is sampled: DUMP_ROWS channels x DUMP_COLS sample
+    positions (16 MB) chosen by a generator with a fixed seed, sorted."""
+    data = sig.data
+    rows, n = data.shape
+    if rows * n * 4 > DUMP_WHOLE_BYTES:
+        import torch
+        rng = np.random.default_rng(1776)
+        r = np.sort(rng.choice(rows, size=min(rows, DUMP_ROWS), replace=False))
+        c = np.sort(rng.choice(n, size=min(n, DUMP_COLS), replace=False))
+        data = data[torch.as_tensor(r, device=data.device)][:, torch.as_tensor(c, device=data.device)]
+    os.makedirs(dirname, exist_ok=True)
+    name = "data.npy" if world == 1 else "data_rank%d.npy" % rank
+    np.save(os.path.join(dirname, name), data.float().cpu().numpy())
+
+
 @contextlib.contextmanager
 def _stdout_to_stderr():
     """fd-level redirect of stdout to stderr: gloo's C++ layer prints its
@@ -552,7 +583,13 @@ def main():
     ap.add_argument("--cpu-chans", type=int, default=32, help="oracle sample size (channels; BASELINE.md §3: 32)")
     ap.add_argument("--cpu-workers", type=int, default=16,
                     help="all-core CPU baseline: concurrent single-threaded oracle processes (0: skip)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes time of its own: the CPU baselines, gpu_power, and for "
+                         "t1/t2 the published disperse stage alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's signal.data (float32; a fixed seeded sample of a large "
+                         "array) to DIR/data.npy")
     ap.add_argument("--backend", choices=("nccl", "gloo"), default="nccl",
                     help="N > 1 process group (nccl = RCCL over xGMI; gloo only to rehearse on one GPU)")
     ap.add_argument("--same-device", action="store_true",
@@ -563,6 +600,8 @@ def main():
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="c3",
                     help="BASELINE config (default: the north-star C3; c4/c5 are extra measurements)")
     args = ap.parse_args()
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs needs the device run (not --dry-run)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
     if args.workload == "c2":
@@ -672,7 +711,7 @@ def main():
             return tutorial_step(pss, args.workload, total, shard, plan_group=pg)
         return c3_step(pss, total, shard, args.log2n, plan_group=pg)
 
-    power = None if args.dry_run else PowerSampler(torch.cuda.current_device())
+    power = PowerSampler(torch.cuda.current_device()) if args.full and not args.dry_run else None
     for _ in range(args.warmup):
         s = step()
         del s
@@ -695,10 +734,13 @@ def main():
     if evs:
         evs[0].record()
     marks = []
+    last = None
     for i in range(args.steps):
         s = step()
         if args.workload == "c4":
             _ = s.data          # fold-mode output is small: materialise it (the gather did when N > 1)
+        if args.dump_outputs and i == args.steps - 1:
+            last = s            # kept for --dump-outputs (written after the timed region)
         del s
         if evs:
             evs[i + 1].record()
@@ -719,6 +761,9 @@ def main():
     if not args.dry_run:
         _lib.load().pss_timing_enable(0)
         launches = _lib.timing_collect()
+    if last is not None:
+        dump_outputs(args.dump_outputs, last, rank, world)
+        del last
     elapsed = t1 - t0
     if world > 1:
         t = torch.tensor([elapsed], device="cpu" if (args.dry_run or args.backend == "gloo") else "cuda",
@@ -798,8 +843,8 @@ def main():
 
     cpu = None
     cpu_all = None
-    # CPU baseline: rank 0 at N=1 only, on the C3 pipeline (the metric's workload)
-    if rank == 0 and world == 1 and not args.no_cpu and not args.dry_run and args.workload == "c3":
+    # CPU baseline (--full): rank 0 at N=1 only, on the C3 pipeline (the metric's workload)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu and not args.dry_run and args.workload == "c3":
         v, dt = cpu_baseline(args.cpu_chans, args.log2n)
         if args.cpu_workers > 0:
             va, dta = cpu_baseline_allcore(args.cpu_workers, 2, args.log2n)
@@ -815,7 +860,7 @@ def main():
                          "out copy, ~2%% of its time, which the GPU run elides when ret_resampsig=False), "
                          "single process, %.1f s on %s" % (args.cpu_chans, args.log2n, dt, cpu_model())}
     tut = None
-    if rank == 0 and world == 1 and not args.dry_run and args.workload in ("t1", "t2"):
+    if args.full and rank == 0 and world == 1 and not args.dry_run and args.workload in ("t1", "t2"):
         # the published stage (disperse alone) next to the reference's own
         # number and the oracle's on this host, same shape
         pub = PUBLISHED[args.workload]
