@@ -330,6 +330,32 @@ int pss_null_shift(const float *row, int64_t count, int64_t *out, void *stream);
 int pss_chi2_fill(float *out, int32_t nrows, int32_t chan0, int64_t n, float df,
                   uint64_t seed, uint32_t call_id, uint32_t purpose, void *stream);
 
+/*
+ * Search-mode output (extension, no reference counterpart).  The input is
+ * data[nchan][ld] float32; a file row r holds the nsblk consecutive samples
+ * [r*nsblk, (r+1)*nsblk) of every channel, rows counted from the `data`
+ * pointer (offset it by whole rows to work in chunks).  One polarisation.
+ *
+ * pss_chan_stats: mn / mx (float32) and sum / sumsq (float64) [nrows][nchan]
+ * of every (row, channel) block.  The float64 sums run in a fixed order
+ * (no atomics): the same input gives the same bits, aligned or not.  A NaN in
+ * a block makes its four values NaN.
+ */
+int pss_chan_stats(const float *data, int32_t nchan, int64_t ld, int64_t nsblk, int64_t nrows,
+                   float *mn, float *mx, double *sum, double *sumsq, void *stream);
+
+/*
+ * pss_quantize_tmajor: out[r][t][c], channel fastest, nchan*nbits/8 bytes per
+ * time sample, nbits in {8, 4, 2}:
+ *   code = clamp(rint((x - offs[r][c]) / scl[r][c]), 0, 2^nbits - 1)
+ * rounding half to even; a NaN x or scl == 0 gives code 0.  For nbits < 8 the
+ * lower-numbered channel takes the more significant bits of its byte.
+ * nchan*nbits must fill whole bytes.  scl / offs are float32 [nrows][nchan]
+ * device arrays.
+ */
+int pss_quantize_tmajor(const float *data, int32_t nchan, int64_t ld, int64_t nsblk, int64_t nrows,
+                        const float *scl, const float *offs, int32_t nbits, void *out, void *stream);
+
 
 #ifdef __cplusplus
 }

@@ -31,6 +31,12 @@ written (an extension).  ``read_fits`` parses any FITS file of binary tables
 parts of it.  The device data is read back once (one D2H copy of the folded
 product; in a multi-GPU run gather it first with
 ``psrsigsim_amd.shard.gather_channels``).
+
+Search mode (``PSRFITS(path, obs_mode="SEARCH")``, no template; an extension:
+the reference leaves it a TODO): the float32 [nchan][nsamp] product is
+quantised to 8 / 4 / 2 bits and transposed to the file's time-major order on
+the device, in chunks of rows (``PSRFITS._save_search``); ``read_search_data``
+unpacks such a file on the host.
 """
 import logging
 import math
@@ -39,7 +45,7 @@ import numpy as np
 
 from .._units import Quantity
 
-__all__ = ["PSRFITS", "read_psrfits", "read_fits", "template_profile"]
+__all__ = ["PSRFITS", "read_psrfits", "read_fits", "read_search_data", "template_profile"]
 
 log = logging.getLogger("psrsigsim_amd")
 
@@ -204,8 +210,10 @@ class PSRFITS(object):
         self._hdus = _raw_hdus(template) if template is not None else None
         if obs_mode is None:
             obs_mode = str(self._hdus[0]["hdr"].get("OBS_MODE", "PSR")).strip() if self._hdus else "PSR"
-        if obs_mode not in ("PSR", "CAL"):
-            raise NotImplementedError("only fold-mode (PSR) output is written")
+        if obs_mode == "SEARCH" and self._hdus is not None:
+            raise NotImplementedError("search-mode output is self-written: the template copy is fold-mode only")
+        if obs_mode not in ("PSR", "CAL", "SEARCH"):
+            raise NotImplementedError("only fold-mode (PSR) and search-mode (SEARCH) output is written")
         self.obs_mode = obs_mode
         self.nchan = self.nbin = self.npol = self.nrows = self.nsblk = self.nsubint = None
         self.tbin = self.obsfreq = self.obsbw = self.chan_bw = self.tsubint = None
@@ -275,10 +283,15 @@ class PSRFITS(object):
 
     # -- save ---------------------------------------------------------------
     def save(self, signal, pulsar, parfile=None, MJD_start=56000.0, segLength=60.0, inc_len=0.0,
-             ref_MJD=56000.0, usePint=True, eq_wts=True, telescope="GBT"):
-        """psrfits.py:305-424 (template) or the self-written layout."""
+             ref_MJD=56000.0, usePint=True, eq_wts=True, telescope="GBT", nbits=8, nsblk=4096, scale="minmax",
+             clip_sigma=(2.0, 6.0), max_stage_bytes=256 << 20):
+        """psrfits.py:305-424 (template) or the self-written layout.  The
+        last five arguments belong to search mode (:meth:`_save_search`)."""
         if self.path is None:
             raise ValueError("no output path")
+        if self.obs_mode == "SEARCH":
+            return self._save_search(signal, pulsar, MJD_start, inc_len, ref_MJD, telescope, nbits, nsblk, scale,
+                                     clip_sigma, max_stage_bytes)
         if self._hdus is None:
             return self._save_new(signal, pulsar, MJD_start, inc_len, ref_MJD, eq_wts, telescope)
         if inc_len == 0.0:
@@ -394,6 +407,26 @@ class PSRFITS(object):
         cards.update(sub_cards)
         return _set_cards(h["cards"], cards), tab.tobytes()
 
+    def _primary_cards(self, signal, pulsar, nchan, dm, MJD_start, inc_len, ref_MJD, telescope):
+        """PRIMARY header cards of the self-written layouts."""
+        if inc_len == 0.0:
+            inc_len = MJD_start - ref_MJD
+        # STT_* (psrfits.py:220-244): integer MJD, integer seconds, fraction
+        start = ref_MJD + (math.floor(inc_len) if inc_len else 0.0)
+        imjd = int(math.floor(start))
+        secs = (start - imjd) * 86400.0 + ((inc_len - math.floor(inc_len)) * 86400.0 if inc_len else 0.0)
+        smjd = int(math.floor(secs))
+        offs = secs - smjd
+        return [
+            _card("SIMPLE", True, "file conforms to FITS standard"), _card("BITPIX", 8), _card("NAXIS", 0),
+            _card("EXTEND", True), _card("HDRVER", "6.1"), _card("FITSTYPE", "PSRFITS"),
+            _card("OBS_MODE", self.obs_mode), _card("TELESCOP", telescope), _card("FRONTEND", "sim"),
+            _card("BACKEND", "psrsigsim_amd"), _card("FD_POLN", "LIN"), _card("SRC_NAME", str(pulsar.name)),
+            _card("OBSFREQ", float(_val(signal.fcent))), _card("OBSBW", float(_val(signal.bw))),
+            _card("OBSNCHAN", nchan), _card("CHAN_DM", dm), _card("STT_IMJD", imjd), _card("STT_SMJD", smjd),
+            _card("STT_OFFS", offs), _card("BE_DELAY", 0.0),
+        ]
+
     def _save_new(self, signal, pulsar, MJD_start, inc_len, ref_MJD, eq_wts, telescope):
         """The self-written layout (no template; extension)."""
         nchan = int(signal.Nchan)
@@ -414,23 +447,7 @@ class PSRFITS(object):
         out = d16.reshape(nchan, nsub, nbin).transpose(1, 0, 2)[:, None, :, :]
         freqs = np.asarray(_val(signal.dat_freq), dtype=np.float64)[:nchan]
         dm = float(_val(signal.dm)) if getattr(signal, "dm", None) is not None else 0.0
-        if inc_len == 0.0:
-            inc_len = MJD_start - ref_MJD
-        # STT_* (psrfits.py:220-244): integer MJD, integer seconds, fraction
-        start = ref_MJD + (math.floor(inc_len) if inc_len else 0.0)
-        imjd = int(math.floor(start))
-        secs = (start - imjd) * 86400.0 + ((inc_len - math.floor(inc_len)) * 86400.0 if inc_len else 0.0)
-        smjd = int(math.floor(secs))
-        offs = secs - smjd
-        primary = [
-            _card("SIMPLE", True, "file conforms to FITS standard"), _card("BITPIX", 8), _card("NAXIS", 0),
-            _card("EXTEND", True), _card("HDRVER", "6.1"), _card("FITSTYPE", "PSRFITS"),
-            _card("OBS_MODE", self.obs_mode), _card("TELESCOP", telescope), _card("FRONTEND", "sim"),
-            _card("BACKEND", "psrsigsim_amd"), _card("FD_POLN", "LIN"), _card("SRC_NAME", str(pulsar.name)),
-            _card("OBSFREQ", float(_val(signal.fcent))), _card("OBSBW", float(_val(signal.bw))),
-            _card("OBSNCHAN", nchan), _card("CHAN_DM", dm), _card("STT_IMJD", imjd), _card("STT_SMJD", smjd),
-            _card("STT_OFFS", offs), _card("BE_DELAY", 0.0),
-        ]
+        primary = self._primary_cards(signal, pulsar, nchan, dm, MJD_start, inc_len, ref_MJD, telescope)
         cols = [(n, "1" + c, None) for n, c in _SUBINT_SCALARS]
         cols += [("DAT_FREQ", "%dD" % nchan, None), ("DAT_WTS", "%dE" % nchan, None),
                  ("DAT_OFFS", "%dE" % (nchan * npol), None), ("DAT_SCL", "%dE" % (nchan * npol), None),
@@ -467,6 +484,167 @@ class PSRFITS(object):
             f.write(_header(primary))
             f.write(_header(sub))
             f.write(_pad(tab.tobytes()))
+
+
+    def _save_search(self, signal, pulsar, MJD_start, inc_len, ref_MJD, telescope, nbits, nsblk, scale,
+                     clip_sigma, max_stage_bytes):
+        """Search-mode file (extension; the reference leaves search mode a
+        TODO): ``nrows = nsamp // nsblk`` SUBINT rows of ``nsblk`` time
+        samples, each sample its ``nchan`` channels as ``nbits``-bit codes,
+        channel fastest, ``value = code * DAT_SCL + DAT_OFFS`` per (row,
+        channel).  The device computes every block's min / max / sums
+        (``pss_chan_stats``), the host derives DAT_OFFS / DAT_SCL from those
+        [nrows][nchan] arrays in float64 --
+
+        * ``scale="minmax"``: DAT_OFFS = min, DAT_SCL = (max - min) / L;
+        * ``scale="sigma"``, ``clip_sigma=(lo, hi)``: DAT_OFFS = mu - lo sigma,
+          DAT_SCL = (lo + hi) sigma / L (values outside clip to 0 / L);
+
+        with L = 2^nbits - 1 -- and the device quantises and transposes
+        (``pss_quantize_tmajor``) chunks of rows of at most ``max_stage_bytes``
+        packed bytes, each copied to a pinned host buffer and appended to the
+        file: neither the packed product nor a host copy of the float data is
+        ever held whole, and ``signal.data`` is not modified.  A constant
+        block gets code 0 everywhere (DAT_SCL 1.0 in the file); so does a
+        block holding a NaN (DAT_OFFS 0, a warning is logged).  A trailing
+        partial block is dropped.  One polarisation."""
+        nchan = int(signal.Nchan)
+        nbits, nsblk = int(nbits), int(nsblk)
+        if nbits not in (8, 4, 2):
+            raise ValueError("search-mode samples are 8, 4 or 2 bits wide, not %d" % nbits)
+        if (nchan * nbits) % 8:
+            raise ValueError("%d channels of %d bits do not fill whole bytes" % (nchan, nbits))
+        if scale not in ("minmax", "sigma"):
+            raise ValueError("scale %r: 'minmax' or 'sigma'" % (scale,))
+        data = signal.data
+        nsamp = int(data.shape[1])
+        nrows = nsamp // nsblk if nsblk >= 1 else 0
+        if nrows == 0:
+            raise ValueError("nsblk %d: %d samples per channel hold no whole block" % (nsblk, nsamp))
+        if int(data.shape[0]) != nchan:
+            raise ValueError("signal.data holds %d channels, Nchan is %d" % (data.shape[0], nchan))
+        if nrows * nsblk < nsamp:
+            log.info("search-mode PSRFITS: dropping the trailing %d samples (partial block of %d)",
+                     nsamp - nrows * nsblk, nsblk)
+        L = (1 << nbits) - 1
+        rowbytes = nsblk * nchan * nbits // 8
+
+        import torch
+        from .. import _engine, _lib
+        if not isinstance(data, torch.Tensor):
+            data = _engine.to_dev(np.asarray(data), dtype=torch.float32)
+        elif data.dtype != torch.float32 or data.stride(1) != 1:
+            data = data.to(torch.float32).contiguous()
+        lib = _lib.lib()
+        dev = data.device
+        ld = max(int(data.stride(0)), nsamp)                   # (a one-channel tensor's stride is arbitrary)
+        mn = torch.empty((nrows, nchan), dtype=torch.float32, device=dev)
+        mx = torch.empty_like(mn)
+        s1 = torch.empty((nrows, nchan), dtype=torch.float64, device=dev)
+        s2 = torch.empty_like(s1)
+        _lib.check(lib.pss_chan_stats(_engine.ptr(data), nchan, ld, nsblk, nrows, _engine.ptr(mn), _engine.ptr(mx),
+                                      _engine.ptr(s1), _engine.ptr(s2), _engine.stream_ptr()), "chan_stats")
+        if scale == "minmax":
+            lo = mn.cpu().numpy().astype(np.float64)
+            offs64 = lo
+            scl64 = (mx.cpu().numpy().astype(np.float64) - lo) / L
+        else:
+            klo, khi = float(clip_sigma[0]), float(clip_sigma[1])
+            mu = s1.cpu().numpy() / nsblk
+            sigma = np.sqrt(np.maximum(s2.cpu().numpy() / nsblk - mu * mu, 0.0))
+            offs64 = mu - klo * sigma
+            scl64 = (klo + khi) * sigma / L
+        with np.errstate(over="ignore", invalid="ignore"):
+            offs = offs64.astype(np.float32)
+            scl_k = scl64.astype(np.float32)                   # the kernel's: 0 -> code 0
+        bad = ~(np.isfinite(offs) & np.isfinite(scl_k))
+        if bad.any():
+            log.warning("search-mode PSRFITS: %d (row, channel) blocks hold NaN or inf; their codes are 0",
+                        int(bad.sum()))
+            offs[bad] = 0.0
+            scl_k[bad] = 0.0
+        scl_file = np.where(scl_k == 0.0, np.float32(1.0), scl_k)
+        d_scl = _engine.to_dev(scl_k)
+        d_offs = _engine.to_dev(offs)
+
+        dm = float(_val(signal.dm)) if getattr(signal, "dm", None) is not None else 0.0
+        tbin = 1.0 / (float(_val(signal.samprate)) * 1e6)
+        tsub = nsblk * tbin
+        freqs = np.asarray(_val(signal.dat_freq), dtype=np.float64)[:nchan]
+        primary = self._primary_cards(signal, pulsar, nchan, dm, MJD_start, inc_len, ref_MJD, telescope)
+        nb = nchan * nbits // 8
+        cols = [(n, "1" + c, None) for n, c in _SUBINT_SCALARS]
+        cols += [("DAT_FREQ", "%dD" % nchan, None), ("DAT_WTS", "%dE" % nchan, None),
+                 ("DAT_OFFS", "%dE" % nchan, None), ("DAT_SCL", "%dE" % nchan, None),
+                 ("DATA", "%dB" % rowbytes, "(1,%d,1,%d)" % (nb, nsblk))]
+        head = np.dtype([(n, _NP[c]) for n, c in _SUBINT_SCALARS] +
+                        [("DAT_FREQ", ">f8", (nchan,)), ("DAT_WTS", ">f4", (nchan,)),
+                         ("DAT_OFFS", ">f4", (nchan,)), ("DAT_SCL", ">f4", (nchan,))])
+        tab = np.zeros(nrows, dtype=head)
+        tab["INDEXVAL"] = np.arange(nrows)
+        tab["TSUBINT"] = tsub
+        tab["OFFS_SUB"] = (np.arange(nrows) + 0.5) * tsub
+        tab["DAT_FREQ"] = freqs
+        tab["DAT_WTS"] = 1.0
+        tab["DAT_OFFS"] = offs
+        tab["DAT_SCL"] = scl_file
+        sub = [_card("XTENSION", "BINTABLE"), _card("BITPIX", 8), _card("NAXIS", 2),
+               _card("NAXIS1", head.itemsize + rowbytes), _card("NAXIS2", nrows), _card("PCOUNT", 0),
+               _card("GCOUNT", 1), _card("TFIELDS", len(cols))]
+        for i, (name, form, dim) in enumerate(cols, 1):
+            sub.append(_card("TTYPE%d" % i, name))
+            sub.append(_card("TFORM%d" % i, form))
+            if dim:
+                sub.append(_card("TDIM%d" % i, dim))
+        sub += [_card("EXTNAME", "SUBINT"), _card("EPOCHS", "MIDTIME"), _card("INT_TYPE", "TIME"),
+                _card("INT_UNIT", "SEC"), _card("NPOL", 1), _card("POL_TYPE", "AA+BB"), _card("TBIN", tbin),
+                _card("NBIN", 1), _card("NCHAN", nchan), _card("CHAN_BW", float(_val(signal.bw)) / nchan),
+                _card("DM", dm), _card("NSBLK", nsblk), _card("NBITS", nbits), _card("ZERO_OFF", 0.0),
+                _card("SIGNINT", 0), _card("NSUBOFFS", 0)]
+
+        chunk = int(max(1, min(nrows, int(max_stage_bytes) // rowbytes)))
+        stage = torch.empty(chunk * rowbytes, dtype=torch.uint8, device=dev)
+        host = torch.empty(chunk * rowbytes, dtype=torch.uint8).pin_memory()
+        host_np = host.numpy()
+        with open(self.path, "wb") as f:
+            f.write(_header(primary))
+            f.write(_header(sub))
+            for r0 in range(0, nrows, chunk):
+                n = min(chunk, nrows - r0)
+                rc = lib.pss_quantize_tmajor(data.data_ptr() + 4 * r0 * nsblk, nchan, ld, nsblk, n,
+                                             d_scl.data_ptr() + 4 * r0 * nchan, d_offs.data_ptr() + 4 * r0 * nchan,
+                                             nbits, _engine.ptr(stage), _engine.stream_ptr())
+                _lib.check(rc, "quantize_tmajor")
+                host[:n * rowbytes].copy_(stage[:n * rowbytes], non_blocking=True)
+                torch.cuda.current_stream().synchronize()
+                for i in range(n):
+                    f.write(tab[r0 + i].tobytes())
+                    f.write(host_np[i * rowbytes:(i + 1) * rowbytes])
+            f.write(b"\0" * ((-nrows * (head.itemsize + rowbytes)) % _BLOCK))
+        self.nchan, self.nrows, self.nsblk, self.tbin, self.npol = nchan, nrows, nsblk, tbin, 1
+
+
+def read_search_data(path):
+    """A search-mode file of :meth:`PSRFITS.save` on the host: ``(codes,
+    values, primary header, SUBINT header)`` with ``codes`` uint8
+    [nchan][nrows * nsblk] (the NBITS-bit samples unpacked: the
+    lower-numbered channel of a byte in its more significant bits) and
+    ``values = codes * DAT_SCL + DAT_OFFS`` (float64 arithmetic, stored as
+    float32) of the same shape."""
+    prim, sub, rec = read_psrfits(path)
+    nbits, nchan, nsblk, nrows = int(sub["NBITS"]), int(sub["NCHAN"]), int(sub["NSBLK"]), int(sub["NAXIS2"])
+    if nbits not in (8, 4, 2) or int(sub.get("NPOL", 1)) != 1:
+        raise NotImplementedError("search-mode data of %d bits, %d polarisations" % (nbits, sub.get("NPOL", 1)))
+    per = 8 // nbits
+    raw = np.ascontiguousarray(rec["DATA"]).reshape(nrows, nsblk, nchan // per)
+    codes = np.empty((nrows, nsblk, nchan), dtype=np.uint8)
+    for p in range(per):
+        codes[:, :, p::per] = (raw >> (8 - nbits * (p + 1))) & ((1 << nbits) - 1)
+    scl = np.asarray(rec["DAT_SCL"], dtype=np.float64).reshape(nrows, 1, nchan)
+    offs = np.asarray(rec["DAT_OFFS"], dtype=np.float64).reshape(nrows, 1, nchan)
+    values = (codes * scl + offs).astype(np.float32)
+    tmajor = lambda a: np.ascontiguousarray(a.reshape(nrows * nsblk, nchan).T)
+    return tmajor(codes), tmajor(values), prim, sub
 
 
 def _parse_header(buf, pos):

@@ -133,11 +133,23 @@ class Simulation(object):
         self.tscope.observe(self.signal, self.pulsar, system=self.system_name, noise=True)
 
     def save_simulation(self, outfile="simfits", out_format='psrfits', parfile=None, ref_MJD=56000.0,
-                        MJD_start=55999.9861):
+                        MJD_start=55999.9861, **search_kw):
         """simulate.py:328-378.  'psrfits' copies the template file with the
         reference's edits (io.PSRFITS; the POLYCO table stays the template's:
         PINT is absent), 'pdv' writes the PSRCHIVE pdv text format
-        (io.TxtFile)."""
+        (io.TxtFile).  'psrfits_search' (extension, no template needed) writes
+        the search-mode signal as a quantised search-mode PSRFITS file;
+        ``search_kw`` are PSRFITS.save's nbits, nsblk, scale, clip_sigma and
+        max_stage_bytes."""
+        if out_format.lower() == 'psrfits_search':
+            from ..io import PSRFITS
+            if outfile == 'simfits':
+                outfile += ".fits"
+            PSRFITS(path=outfile, obs_mode='SEARCH').save(self.signal, self.pulsar, MJD_start=MJD_start,
+                                                          ref_MJD=ref_MJD, **search_kw)
+            return
+        if search_kw:
+            raise TypeError("unexpected arguments for out_format %r: %s" % (out_format, sorted(search_kw)))
         if out_format.lower() == 'psrfits':
             from ..io import PSRFITS
             from ..utils import make_par
