@@ -30,11 +30,23 @@
 //   * column blocks of the column passes mapped XCD-contiguously (xcd_block);
 //   * 2^22 split 1024 x 4096 (rows of 4096 for 2^17 .. 2^22), 2^24 split
 //     2048 x 8192;
-//   * fast pass C on 16-column blocks of 1024 threads (C3), 16-column
-//     register-resident blocks of 512 threads (C5, passC_fast32);
+//   * fast pass C, 16-column blocks (64-B output segments) wherever the
+//     columns have 1024 points or more: passC_fast32, register-resident
+//     columns in 512-thread workgroups -- 1024-point columns (2^22 = C3, 2^23,
+//     C5's 1024 x 16384) at the 128-VGPR cap with 72 KB of LDS, two workgroups
+//     per CU ("C:fast C:cols16x2"); 2048-point columns (2^24 with a delayed
+//     null, 2048 x 8192) at 256 VGPRs, one workgroup per CU ("C:fast32").
+//     Shorter columns (2^14 .. 2^21) and the mixed-radix splits: passC_fast,
+//     the block in LDS, on pass A's block width ("C:fast");
 //   * the delayed-null mask table built on a side stream next to pass A, and
 //     applied by the compacted fix-up (k_null_fix_list) after pass C.
-static constexpr int kBC = 16, kTC = 1024;   // fast pass C block / threads (C3 and 2^17 .. 2^21)
+static constexpr int kBC = 16, kTC = 1024;   // LDS-resident fast pass C block / threads (passC_fast)
+// 1024-point columns: the register-resident fast pass C at two workgroups per
+// CU (0: passC_fast, the A/B partner -- build.py --variant NAME -DPSS_PASSC_COLS16=0)
+#ifndef PSS_PASSC_COLS16
+#define PSS_PASSC_COLS16 1
+#endif
+static constexpr bool kPassCCols16 = PSS_PASSC_COLS16 != 0;
 
 using namespace pss;
 
@@ -2062,22 +2074,28 @@ struct PairCols<N1, B, T, RList<F...>, RList<I...>, XRS> {
         }
     }
 
-    // C, fast path (host-selected: Philox draws with df = 1 for the noise, no
-    // injected draws, no observe() copy).  Bitwise equal to passC: every
-    // sample is stored as signal + noise; a delayed null's samples are
-    // rewritten afterwards by k_null_fix_list (fusing the table lookups here
-    // measured 27.0 ms against 16.6 + 2.5 for pass C + fix-up, round 2).
-    // C, fast path with register-resident columns (C5's 2048-point columns,
-    // 16 columns per 512-thread workgroup: 64-B output segments per channel
-    // row instead of 32; tools/seg_bw.hip: 64-B write segments run at 5.2
-    // TB/s against 3.1 for 32 B).  16 columns of 2048 rows are 256 KB, so
-    // they cannot all sit in LDS: each wave keeps its columns in registers
-    // between three LDS phases --
-    // (1) the spill rows in two halves of 512 (256-B row segments, twiddled as
-    // in inv_block) staged in LDS and picked up into the FFT input mapping,
+    // C, fast path with register-resident columns: 16 columns of 1024 or 2048
+    // points per 512-thread workgroup (64-B output segments per channel row;
+    // tools/seg_bw.hip: 64-B write segments run at 5.2 TB/s against 3.1 for
+    // 32 B).  Each wave keeps its two columns in registers between three LDS
+    // phases --
+    // (1) the spill rows in two halves of N1/2 (128-B row segments, twiddled
+    // as in inv_block) staged in LDS and picked up into the FFT input mapping,
     // (2) the two wave-local inverse FFTs one after the other through the
     // wave's own LDS row, (3) each channel's scaled outputs staged as
-    // [n1][33] floats and stored as whole 128-B row segments with the noise.
+    // [n1][17] floats and stored as whole 64-B row segments with the noise --
+    // so the LDS buffer is half a block, one FFT row per wave or one
+    // channel's outputs, whichever is largest, not the whole block.
+    //   * 2048-point columns (2^24 with a delayed null): the whole block
+    //     would be 256 KB and cannot sit in LDS at all; 139 392 B here, 128
+    //     VGPRs of columns per lane (k_pairC_fast32 at 2 waves per SIMD), one
+    //     workgroup per CU.
+    //   * 1024-point columns (2^22, 2^23, C5's 1024 x 16384): passC_fast's
+    //     139 392-B block leaves one 1024-thread workgroup per CU, every barrier
+    //     putting all 16 waves of the CU in the same phase; 69 760 B + tw16 =
+    //     71 936 B here and 64 VGPRs of columns (4 waves per SIMD, the
+    //     128-VGPR cap: 94 used, no scratch), so two workgroups share a CU and
+    //     one loads or stores while the other transforms.
     // Bitwise the values of passC_fast (same twiddles, FFT and epilogue).
     __device__ static void passC_fast32(const KP &k) {
         static_assert((N1 == 1024 || N1 == 2048) && (T == 1024 || T == 512) && B % (T / 64) == 0 &&
@@ -2109,6 +2127,13 @@ struct PairCols<N1, B, T, RList<F...>, RList<I...>, XRS> {
         const uint32_t RP = (uint32_t)rpitch(k);
         cf *hb = reinterpret_cast<cf *>(smem);
         cf v[CPW][E1];
+        // The 1024-point form runs at the 128-VGPR cap (two workgroups per
+        // CU) with 64 VGPRs of columns: each phase takes its thread indices
+        // through opaque(), so that address arithmetic of a later phase (or of
+        // the second column's FFT, identical to the first's) is recomputed
+        // where it is used instead of being held in registers -- spilled --
+        // across the FFTs (as PairRowsSeq).
+        auto fresh = [](int x) __attribute__((always_inline)) { return N1 == 1024 ? opaque(x) : x; };
         // (1) spill rows, two halves
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
@@ -2152,7 +2177,7 @@ struct PairCols<N1, B, T, RList<F...>, RList<I...>, XRS> {
 #pragma unroll
             for (int c = 0; c < CPW; ++c) {
                 if (c) stage_sync<true>();
-                FWC::template run_tw<true, 1, I...>(v[c], wl, lane, tw16);
+                FWC::template run_tw<true, 1, I...>(v[c], wl, fresh(lane), tw16);
             }
         }
         // (3) per channel: stage the scaled outputs, store rows with the noise
@@ -2164,10 +2189,11 @@ struct PairCols<N1, B, T, RList<F...>, RList<I...>, XRS> {
 #pragma unroll
         for (int ch = 0; ch < 2; ++ch) {
             __syncthreads();                            // FFT rows / previous channel's staging free
+            const int sl = fresh(lane);
 #pragma unroll
             for (int i = 0; i < E1; ++i) {
                 int bb, pos;
-                FWC::template where<RIL>(i, lane, bb, pos);
+                FWC::template where<RIL>(i, sl, bb, pos);
 #pragma unroll
                 for (int c = 0; c < CPW; ++c) stg[pos * OSP + wv + NW * c] = (ch ? v[c][i].y : v[c][i].x) * invN;
             }
@@ -2176,9 +2202,10 @@ struct PairCols<N1, B, T, RList<F...>, RList<I...>, XRS> {
             if (!has) continue;                         // (uniform)
             const uint32_t c = ch ? cb : ca;
             const Buf o(p.data + (int64_t)(ch ? rb : ra) * p.ld, rbytes);
+            const int t0 = fresh(tid);
 #pragma unroll
             for (int t = 0; t < N1 * B / 4 / T; ++t) {
-                const int it = tid + t * T;
+                const int it = t0 + t * T;
                 const int n1 = it / (B / 4), c4 = (it - n1 * (B / 4)) * 4;
                 const uint32_t n = (uint32_t)(n1 * (int)N2) + (uint32_t)n20 + (uint32_t)c4;
                 const float4 x = chi2_1x4(gn.bits(n >> 2, c, 0u));
@@ -2189,6 +2216,12 @@ struct PairCols<N1, B, T, RList<F...>, RList<I...>, XRS> {
         }
     }
 
+    // C, fast path (host-selected: Philox draws with df = 1 for the noise, no
+    // injected draws, no observe() copy), the whole column block in LDS.
+    // Bitwise equal to passC: every sample is stored as signal + noise; a
+    // delayed null's samples are rewritten afterwards by k_null_fix_list
+    // (fusing the table lookups here measured 27.0 ms against 16.6 + 2.5 for
+    // pass C + fix-up, round 2).
     __device__ static void passC_fast(const KP &k) {
         static_assert(kItemsExact, "fast pass C: whole items per thread");
         __shared__ __align__(128) cf lds[B * LdsC::RS];
@@ -2273,8 +2306,11 @@ template <typename C, int T>
 __global__ __launch_bounds__(T) void k_pairC(KP k) { C::passC(k); }
 template <typename C, int T>
 __global__ __launch_bounds__(T) void k_pairC_fast(KP k) { C::passC_fast(k); }
-template <typename C, int T>
-__global__ __launch_bounds__(T, T == 512 ? 2 : 4) void k_pairC_fast32(KP k) { C::passC_fast32(k); }
+// W: min waves per SIMD.  512 threads at 2 (256 VGPRs) for the 2048-point
+// columns (64 complex values per lane); at 4 (128 VGPRs) for the 1024-point
+// columns, whose 72 KB of LDS then lets two workgroups share a CU.
+template <typename C, int T, int W = (T == 512 ? 2 : 4)>
+__global__ __launch_bounds__(T, W) void k_pairC_fast32(KP k) { C::passC_fast32(k); }
 template <typename C, int T>
 __global__ __launch_bounds__(T) void k_node_col(KP k, float *nodes) { C::node_col(k, nodes); }
 // (4 waves per SIMD for columns up to 30: the compiler would otherwise keep
@@ -2832,6 +2868,10 @@ static int launch_pair_passes(KP &k, hipStream_t st, const float *mask_after_a) 
                 k_pairC_fast32<PairCols<N1, 16, 512, CF, CI, -1>, 512>
                     <<<dim3((unsigned)(N2 / 16), (unsigned)k.npairs), dim3(512), 0, st>>>(k);
                 plan_note(" C:fast32");
+            } else if constexpr (kPassCCols16 && N1 == 1024 && N2 % 16 == 0) {
+                k_pairC_fast32<PairCols<N1, 16, 512, CF, CI, -1>, 512, 4>
+                    <<<dim3((unsigned)(N2 / 16), (unsigned)k.npairs), dim3(512), 0, st>>>(k);
+                plan_note(" C:fast C:cols16x2");
             } else {
                 k_pairC_fast<PCC, TC><<<dim3((unsigned)(N2 / BC), (unsigned)k.npairs), dim3(TC), 0, st>>>(k);
                 plan_note(" C:fast");
