@@ -356,6 +356,33 @@ int pss_chan_stats(const float *data, int32_t nchan, int64_t ld, int64_t nsblk, 
 int pss_quantize_tmajor(const float *data, int32_t nchan, int64_t ld, int64_t nsblk, int64_t nrows,
                         const float *scl, const float *offs, int32_t nbits, void *out, void *stream);
 
+/*
+ * Baseband channeliser and detector (extension, no reference counterpart).
+ * x[npol][ld] float32 voltages (npol = 1 or 2, n samples per row), C = nchan a
+ * power of two in [16, 4096], L = 2 C, T = ntap in [1, 8], h[T L] the
+ * prototype filter (all ones for T = 1):
+ *   y_m[j]    = sum_{t<T} h[t L + j] x[(m + t) L + j]            (j < L)
+ *   X_m[k]    = sum_j y_m[j] exp(-2 pi i j k / L)
+ *   out[k][s] = 1 / (L tscrunch) sum_pol sum_{m = s tscrunch}^{(s+1) tscrunch - 1} |X_m[k]|^2
+ * for k < C (bin 0 kept, the Nyquist bin dropped) and s < S = floor(M /
+ * tscrunch), M = floor(n / L) - T + 1 spectra; trailing samples and a ragged
+ * last group are dropped.  out is [C][out_ld] float32, written once; x is read
+ * once.  Sums run in a fixed order: the same input gives the same bits.
+ * PSS_EINVAL (nothing launched) on NULL pointers, ld < n, out_ld < S or a
+ * parameter out of range; PSS_OK with nothing launched when S < 1.
+ */
+int pss_channelize(const float *x, int32_t npol, int64_t n, int64_t ld, const float *h, int32_t nchan,
+                   int32_t ntap, int32_t tscrunch, float *out, int64_t out_ld, void *stream);
+
+/*
+ * Amplitude radiometer noise (receiver.py:123-138): rows[r][i] += scale *
+ * N(0, 1) for r < nrows, i < n, in place and stream-ordered.  The draws are
+ * the Philox Box-Muller normals of the amplitude pulses, purpose P_NOISE,
+ * keyed (seed, call_id, r, i): independent of the launch geometry.
+ */
+int pss_normal_add(float *rows, int32_t nrows, int64_t n, int64_t ld, float scale, uint64_t seed,
+                   uint32_t call_id, void *stream);
+
 
 #ifdef __cplusplus
 }

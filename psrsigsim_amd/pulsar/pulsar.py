@@ -131,6 +131,7 @@ class Pulsar(object):
         call = _engine.next_call()
         inj = _engine.take_injection("gen")
         signal._nsamp = int((tobs * sr) * 1e6)
+        signal._period_s = P                  # Backend.channelize: the subint length of the detected signal
         spp = (sr * P) * 1e6
         inv = 1.0 / spp
         step = int(round(math.ldexp(inv - math.floor(inv), 64)))

@@ -7,7 +7,7 @@ in the epilogue of the fused run (full resolution, in place, unclipped).
 import numpy as np
 
 from .._units import make_quant, to_value
-from .. import _engine
+from .. import _engine, _lib
 
 __all__ = ['Receiver']
 
@@ -65,14 +65,47 @@ class Receiver(object):
             Tsys = make_quant(Tenv, 'K') + self.Trec
         gain = make_quant(gain, "K/Jy")
         if signal.sigtype in ["RFSignal", "BasebandSignal"]:
-            raise NotImplementedError("amplitude noise is outside the filterbank path")
+            self._make_amp_noise(signal, Tsys, gain, pulsar)
         elif signal.sigtype == "FilterBankSignal":
             self._make_pow_noise(signal, Tsys, gain, pulsar)
         else:
             raise NotImplementedError("no pulse method for signal: {}".format(signal.sigtype))
 
+    @staticmethod
+    def amp_noise_norm(signal, pulsar, Tsys, gain):
+        """receiver.py:126-135 scale, planned on the host in float64:
+        sigS = Tsys/gain/sqrt(2 dt bw) with dt = 1/samprate (Jy), U_scale =
+        1/(sum(max_profile)/samprate), norm = sqrt(sigS/Smax) * U_scale.
+
+        Parity hazard (kept): the reference divides the profile sum by the
+        sample rate as a quantity in MHz and then drops the unit
+        (``noise.value``), so U_scale -- and the noise amplitude -- carries the
+        sample rate's numerical value in MHz, not a count of phase bins as the
+        power path's nbins does."""
+        Tsys_K = float(to_value(make_quant(Tsys, 'K'), 'K'))
+        gain_v = float(to_value(make_quant(gain, 'K/Jy'), 'K/Jy'))
+        sr = float(to_value(signal.samprate, 'MHz'))
+        bw = float(to_value(signal.bw, 'MHz'))
+        dt = 1.0 / sr
+        sigS = Tsys_K / gain_v / np.sqrt(2 * dt * bw)                       # Jy
+        U_scale = 1.0 / (np.sum(pulsar.Profiles._max_profile) / sr)
+        Smax = float(to_value(signal._Smax, 'Jy'))
+        return float(np.sqrt(sigS / Smax) * U_scale)
+
     def _make_amp_noise(self, signal, Tsys, gain, pulsar):
-        raise NotImplementedError("amplitude noise is outside the filterbank path")
+        """receiver.py:123-138: data += norm * N(0, 1) on every row, in place
+        on the device (``pss_normal_add``: the Philox Box-Muller normals of the
+        amplitude pulses, keyed seed / call id / row / sample), in stream order
+        with no host synchronisation.  Pending stages run first."""
+        if signal.sigtype != "BasebandSignal":
+            raise NotImplementedError("RFSignal is not built (baseband and filterbank only)")
+        norm = self.amp_noise_norm(signal, pulsar, Tsys, gain)
+        call = _engine.next_call()
+        data = signal.data                                    # flushes pending stages
+        rows, n = data.shape
+        rc = _lib.lib().pss_normal_add(_engine.ptr(data), rows, n, max(int(data.stride(0)), n), float(norm),
+                                       _engine._state["seed"], call, _engine.stream_ptr())
+        _lib.check(rc, "normal_add")
 
     @staticmethod
     def noise_norm(signal, pulsar, Tsys, gain):
