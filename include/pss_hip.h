@@ -383,6 +383,28 @@ int pss_channelize(const float *x, int32_t npol, int64_t n, int64_t ld, const fl
 int pss_normal_add(float *rows, int32_t nrows, int64_t n, int64_t ld, float scale, uint64_t seed,
                    uint32_t call_id, void *stream);
 
+/*
+ * Incoherent dedispersion over trial DMs (extension, no reference
+ * counterpart): the DM-time plane of data[nchan][ld] float32 (n samples per
+ * row) for the device table delays[ndm][nchan] of int32 sample delays.  With
+ * T = n - max_delay:
+ *   d(j, c)   = min(max(delays[j * nchan + c], 0), max_delay)
+ *   out[j][t] = sum_{c < nchan} data[c * ld + t + d(j, c)],   t < T, j < ndm
+ * the exact direct sum.  The table is arbitrary (it need not be monotone in c
+ * or j); because of the clamp no read leaves [0, n) of its row whatever it
+ * holds, and nothing is written outside out[j * out_ld + 0 .. T).  A workgroup
+ * owns 2048 times of 8 neighbouring trials; a channel whose delays differ by
+ * at most 2044 samples among those 8 trials is read from global memory once
+ * for all of them (staged in LDS), a channel with a wider spread once per
+ * trial.  Every out[j][t] is summed in increasing c by one thread, without
+ * atomics: the same input gives the same bits from run to run, and whatever
+ * the alignment of data / ld / out / out_ld.  No workspace.
+ * PSS_EINVAL (nothing launched) on a NULL pointer, nchan < 1, ndm < 1,
+ * ld < n, max_delay < 0, max_delay >= n or out_ld < T, and when
+ * ceil(T / 2048) * ceil(ndm / 8) exceeds 2^31 - 1 (the launch grid).
+ */
+int pss_dedisperse(const float *data, int32_t nchan, int64_t n, int64_t ld, const int32_t *delays,
+                   int32_t ndm, int32_t max_delay, float *out, int64_t out_ld, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,250 @@
+// pss_dedisperse.hip -- incoherent dedispersion over trial DMs (extension, no
+// reference counterpart): the DM-time plane of a [chan][time] filterbank,
+//
+//   out[j][t] = sum_{c < nchan} data[c][t + d(j, c)],   t < T = n - max_delay,
+//
+// the exact direct sum over an arbitrary integer delay table d[ndm][nchan]
+// (clamped to [0, max_delay] as it is loaded).
+//
+//   k_dedisperse<VEC> : a workgroup of 256 threads owns kTB = 2048 output times
+//       of kND = 8 neighbouring trials and walks the channels in order, kCB = 2
+//       per barrier pair.  Lanes run along time: thread i holds times
+//       t0 + i + 256 k (k < 8) of each of its trials, 64 accumulators.
+//       Per channel c, with dmin / dmax the extreme delays of the workgroup's
+//       trials (wave-uniform, scalar loads of the table):
+//         staged  (dmax - dmin <= kSpread = 2044): the window
+//                 data[c][ws .. t0 + dmax + 2048), ws = (t0 + dmin) & ~3, is
+//                 copied to LDS once (16-B loads when the row is on the 16-B
+//                 grid, VEC, all issued before the first LDS store; dwords
+//                 otherwise -- the same values) and every
+//                 trial reads its 8 samples per lane from it at the uniform
+//                 offset t0 + d - ws: consecutive lanes read consecutive
+//                 dwords, conflict-free at any offset.  The channel's row is
+//                 read from global memory once per 8 trials.
+//         wide    (a wider spread): the general path.  The trials take turns,
+//                 two at a time: each copies its own samples
+//                 data[c][t0 + d .. + 2048) into half of the channel's LDS
+//                 buffer (dword loads), between two barriers, and reads them
+//                 back the same way -- one global read of the row per trial.
+//       Either way a sample joins its accumulator as `acc += x` in increasing
+//       c, so the bits of out[j][t] depend on neither the path, the alignment
+//       nor the launch geometry.  No atomics, no workspace.
+//       The finished tile goes to out[j][t0 ..] as dword stores, 256 B per
+//       wave-instruction.
+//       Logical workgroup index = time tile * (trial groups) + trial group,
+//       dealt to the XCDs in contiguous runs: the groups of one time tile run
+//       together on one XCD and share its rows in that L2.
+#include "pss_engine.hpp"
+
+using namespace pss;
+
+static constexpr int kDdThreads = 256;
+static constexpr int kDdS = 8;                        // samples per lane and trial
+static constexpr int kTB = kDdThreads * kDdS;         // output times per workgroup
+static constexpr int kND = 8;                         // trials per workgroup
+// channels per barrier pair, and trials whose LDS reads are in flight together
+// (A/B builds: build.py --variant NAME -DPSS_DD_CB=n -DPSS_DD_NJ=n)
+#ifndef PSS_DD_CB
+#define PSS_DD_CB 2
+#endif
+#ifndef PSS_DD_NJ
+#define PSS_DD_NJ 2
+#endif
+static constexpr int kCB = PSS_DD_CB;
+static constexpr int kNJ = PSS_DD_NJ;
+static constexpr int kWin = 2 * kTB;                  // staged window, floats per channel
+static_assert(kNJ * kTB <= kWin && kND % kNJ == 0, "the wide path's trials share the window");
+static constexpr int kSpread = kWin - kTB - 4;        // widest staged spread of a channel's delays
+
+struct DdArgs {
+    int64_t n, ld, out_ld, T;
+    int32_t nchan, ndm, max_delay, ngroups;
+};
+
+// row[ws .. ws + need) -> w[0 .. need), ws % 4 == 0, whole 16-B groups; samples
+// at or past n (never needed) are zeros
+template <bool VEC>
+__device__ __forceinline__ void dd_stage(float *w, const float *row, int64_t ws, int need, int64_t n, int tid) {
+    PSS_DASSERT(need >= 1 && need <= kWin && ws >= 0 && ws + need <= n);
+    const int nq = (need + 3) >> 2;                     // 16-B groups, <= kWin / 4
+    if (VEC && ws + 4 * (int64_t)nq <= n) {
+        // every group inside the row (all but a row's last tile): the loads of
+        // all passes are issued, unconditionally, before the first LDS store
+        // waits for one -- a load-store loop pays one global latency per pass.
+        // The lanes past the last group re-load it (in bounds, one cache line
+        // for all of them); a pass with work stores every lane's value, the
+        // copies in slots of the window that no stored sum reads.
+        constexpr int NP = kWin / 4 / kDdThreads;
+        const float4 *src = reinterpret_cast<const float4 *>(row + ws);
+        float4 v[NP];
+#pragma unroll
+        for (int i = 0; i < NP; ++i) v[i] = src[min(tid + i * kDdThreads, nq - 1)];
+        // (pinned here, or each load sinks into the branch of its store)
+#pragma unroll
+        for (int i = 0; i < NP; ++i) asm volatile("" : "+v"(v[i].x), "+v"(v[i].y), "+v"(v[i].z), "+v"(v[i].w));
+#pragma unroll
+        for (int i = 0; i < NP; ++i)
+            if (i * kDdThreads < nq) *reinterpret_cast<float4 *>(w + 4 * (tid + i * kDdThreads)) = v[i];
+        return;
+    }
+    for (int q = tid; q < nq; q += kDdThreads) {
+        const int64_t s = ws + 4 * q;
+        float4 v;
+        v.x = s < n ? row[s] : 0.0f;
+        v.y = s + 1 < n ? row[s + 1] : 0.0f;
+        v.z = s + 2 < n ? row[s + 2] : 0.0f;
+        v.w = s + 3 < n ? row[s + 3] : 0.0f;
+        *reinterpret_cast<float4 *>(w + 4 * q) = v;
+    }
+}
+
+// acc[i][k] += w[off[i] + tid + 256 k] for NJ trials: off <= kWin - kTB, so the
+// reads stay inside the window whatever the tile's length (a short tile's lanes
+// past `len` add stale LDS words to accumulators that are never stored)
+template <int NJ>
+__device__ __forceinline__ void dd_accum(float (*acc)[kDdS], const float *w, const int (&off)[NJ], int tid) {
+#pragma unroll
+    for (int i = 0; i < NJ; ++i) {
+        PSS_DASSERT(off[i] >= 0 && off[i] + kTB <= kWin);
+        const float *p = w + off[i] + tid;
+#pragma unroll
+        for (int k = 0; k < kDdS; ++k) acc[i][k] += p[k * kDdThreads];
+    }
+    // NJ trials' reads (8 each) in flight at a time: the sums are pinned here (an
+    // empty asm that "modifies" them) and nothing is scheduled across.
+    // Otherwise the adds sink below the following trials' reads, 64 loaded
+    // values stay live beside the 64 accumulators, and two waves per SIMD are
+    // lost (144 registers)
+#pragma unroll
+    for (int i = 0; i < NJ; ++i)
+#pragma unroll
+        for (int k = 0; k < kDdS; ++k) asm volatile("" : "+v"(acc[i][k]));
+    __builtin_amdgcn_sched_barrier(0);
+}
+
+// (the pointers are separate __restrict__ parameters: the table is then known
+// not to alias `out`, and its wave-uniform loads become scalar loads)
+template <bool VEC>
+__global__ __launch_bounds__(kDdThreads) void k_dedisperse(const float *__restrict__ data,
+                                                           const int32_t *__restrict__ tab, float *__restrict__ out,
+                                                           DdArgs a) {
+    __shared__ __align__(16) float win[kCB][kWin];
+    const int tid = threadIdx.x;
+    // Workgroup id -> (time tile, trial group), groups fastest, through the XCD
+    // map: ids are dealt to the 8 XCDs round-robin, so XCD x is given the
+    // contiguous run of logical ids [x base + min(x, rem), ..): the trial groups
+    // of one time tile then run on one XCD, side by side, and its L2 fetches
+    // each row once for all of them.  Placement only changes the speed.
+    const unsigned total = gridDim.x, base = total >> 3, rem = total & 7u;
+    const unsigned xcd = blockIdx.x & 7u;
+    const unsigned lid = xcd * base + min(xcd, rem) + (blockIdx.x >> 3);
+    const int g = (int)(lid % (unsigned)a.ngroups);
+    const int64_t t0 = (int64_t)(lid / (unsigned)a.ngroups) * kTB;
+    const int j0 = g * kND;
+    const int nd = min(kND, a.ndm - j0);                       // trials of this group (>= 1)
+    const int len = (int)min((int64_t)kTB, a.T - t0);          // times of this tile (>= 1)
+    float acc[kND][kDdS];
+#pragma unroll
+    for (int j = 0; j < kND; ++j)
+#pragma unroll
+        for (int k = 0; k < kDdS; ++k) acc[j][k] = 0.0f;
+
+    for (int c0 = 0; c0 < a.nchan; c0 += kCB) {
+        int d[kCB][kND];
+        int64_t ws[kCB];
+        bool staged[kCB];
+#pragma unroll
+        for (int cb = 0; cb < kCB; ++cb) {
+            const int c = c0 + cb;
+            staged[cb] = false;
+            ws[cb] = 0;
+            if (c >= a.nchan) continue;
+            int dmin = a.max_delay, dmax = 0;
+#pragma unroll
+            for (int j = 0; j < kND; ++j) {
+                // (a ragged group repeats its last trial: summed, never stored)
+                const int jj = j0 + min(j, nd - 1);
+                d[cb][j] = min(max(tab[(int64_t)jj * a.nchan + c], 0), a.max_delay);
+                dmin = min(dmin, d[cb][j]);
+                dmax = max(dmax, d[cb][j]);
+            }
+            if (dmax - dmin > kSpread) continue;
+            staged[cb] = true;
+            ws[cb] = (t0 + dmin) & ~(int64_t)3;
+            // the window's last needed sample is t0 + len - 1 + dmax <= n - 1
+            const int need = (int)(t0 + dmax - ws[cb]) + len;  // <= 3 + kSpread + kTB < kWin
+            dd_stage<VEC>(win[cb], data + (int64_t)c * a.ld, ws[cb], need, a.n, tid);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int cb = 0; cb < kCB; ++cb) {
+            const int c = c0 + cb;
+            if (c >= a.nchan) continue;
+            // (one accumulate serves both paths: an if / else around two copies of
+            // it joins the 64 accumulators in phis that cost 60 more registers)
+            const float *row = data + (int64_t)c * a.ld + t0;
+#pragma unroll
+            for (int j = 0; j < kND; j += kNJ) {
+                int off[kNJ];
+#pragma unroll
+                for (int i = 0; i < kNJ; ++i) off[i] = staged[cb] ? (int)(t0 + d[cb][j + i] - ws[cb]) : i * kTB;
+                if (!staged[cb]) {
+                    // wide: the channel's own (unused) window serves kNJ trials at a
+                    // time, trial i's samples t0 + d .. + len at i * kTB (dword loads:
+                    // t + d <= T - 1 + max_delay = n - 1)
+#pragma unroll
+                    for (int i = 0; i < kNJ; ++i)
+                        for (int q = tid; q < len; q += kDdThreads) win[cb][i * kTB + q] = row[d[cb][j + i] + q];
+                    __syncthreads();
+                }
+                dd_accum<kNJ>(&acc[j], win[cb], off, tid);
+                if (!staged[cb]) __syncthreads();
+            }
+        }
+        __syncthreads();      // the next pair of channels overwrites the windows
+    }
+#pragma unroll
+    for (int j = 0; j < kND; ++j) {
+        if (j < nd) {
+            float *o = out + (int64_t)(j0 + j) * a.out_ld + t0 + tid;
+#pragma unroll
+            for (int k = 0; k < kDdS; ++k)
+                if (tid + k * kDdThreads < len) o[k * kDdThreads] = acc[j][k];
+        }
+    }
+}
+
+extern "C" {
+
+int pss_dedisperse(const float *data, int32_t nchan, int64_t n, int64_t ld, const int32_t *delays, int32_t ndm,
+                   int32_t max_delay, float *out, int64_t out_ld, void *stream) {
+    if (!data) return fail(PSS_EINVAL, "dedisperse: data is NULL");
+    if (!delays) return fail(PSS_EINVAL, "dedisperse: delays is NULL");
+    if (!out) return fail(PSS_EINVAL, "dedisperse: out is NULL");
+    if (nchan < 1) return fail(PSS_EINVAL, "dedisperse: nchan %d < 1", nchan);
+    if (ndm < 1) return fail(PSS_EINVAL, "dedisperse: ndm %d < 1", ndm);
+    if (ld < n) return fail(PSS_EINVAL, "dedisperse: ld %lld < n %lld", (long long)ld, (long long)n);
+    if (max_delay < 0) return fail(PSS_EINVAL, "dedisperse: max_delay %d < 0", max_delay);
+    if (max_delay >= n) return fail(PSS_EINVAL, "dedisperse: max_delay %d >= n %lld", max_delay, (long long)n);
+    const int64_t T = n - max_delay;
+    if (out_ld < T) return fail(PSS_EINVAL, "dedisperse: out_ld %lld < %lld output samples", (long long)out_ld,
+                                (long long)T);
+    const int64_t ngroups = ((int64_t)ndm + kND - 1) / kND;
+    const int64_t ntiles = (T + kTB - 1) / kTB;
+    if (ntiles > (int64_t)0x7fffffff / ngroups)
+        return fail(PSS_EINVAL, "dedisperse: %lld time tiles x %lld trial groups exceed 2^31 - 1 workgroups",
+                    (long long)ntiles, (long long)ngroups);
+    DdArgs a;
+    a.n = n; a.ld = ld; a.nchan = nchan; a.ndm = ndm; a.max_delay = max_delay;
+    a.ngroups = (int32_t)ngroups; a.out_ld = out_ld; a.T = T;
+    const dim3 grid((unsigned)(ntiles * ngroups));
+    // 16-B loads of the staged windows need the rows on the 16-B grid.  Same bits.
+    if ((uintptr_t)data % 16 == 0 && ld % 4 == 0)
+        k_dedisperse<true><<<grid, dim3(kDdThreads), 0, (hipStream_t)stream>>>(data, delays, out, a);
+    else
+        k_dedisperse<false><<<grid, dim3(kDdThreads), 0, (hipStream_t)stream>>>(data, delays, out, a);
+    LAUNCHCHK();
+    return PSS_OK;
+}
+
+}  // extern "C"

@@ -3,9 +3,34 @@ import numpy as np
 import torch
 
 from .._units import make_quant, to_value
+from ..utils.constants import DM_K_VALUE
 from .. import _engine, _lib
 
-__all__ = ['Backend']
+__all__ = ['Backend', 'DedispersedPlane']
+
+
+class DedispersedPlane(object):
+    """Result of :meth:`Backend.dedisperse`: the DM-time plane on the device.
+
+    ``data``      torch float32 [nDM, T] (T = N - max_delay), row j the sum over
+                  the channels of the signal shifted by ``delays[j]``
+    ``dms``       the trial DMs, float64 [nDM] (pc/cm^3)
+    ``delays``    the host table, int32 [nDM][C_local] samples
+    ``samprate``  sample rate of the series, MHz
+    ``ref_freq``  the frequency the delays refer to, MHz
+    ``max_delay`` the table's maximum, samples"""
+
+    def __init__(self, data, dms, delays, samprate, ref_freq, max_delay):
+        self.data = data
+        self.dms = dms
+        self.delays = delays
+        self.samprate = samprate
+        self.ref_freq = ref_freq
+        self.max_delay = max_delay
+
+    def __repr__(self):
+        return "DedispersedPlane(%d trials x %d samples, ref %.6g MHz)" % (
+            self.data.shape[0], self.data.shape[1], self.ref_freq)
 
 
 class Backend(object):
@@ -142,6 +167,90 @@ class Backend(object):
         fb._null_error = None
         fb._null_checks = []
         return fb
+
+    @staticmethod
+    def dedisperse_delays(signal, dms, ref_freq=None):
+        """The integer delay table of :meth:`dedisperse` (host only, float64;
+        nothing touches the device): int32 [nDM][C_local],
+
+            x[j][c] = DM_K_VALUE * dms[j] * (f_c**-2 - f_ref**-2) [s] * samprate [Hz]
+            d[j][c] = int(floor(x[j][c] + 0.5))
+
+        with f_c the channel's entry in ``signal.dat_freq`` -- its lower edge,
+        the frequency ``ISM.disperse`` delays it by -- so the DM that was
+        injected undoes the sweep to within half a sample per channel.
+        ``ref_freq`` (MHz) defaults to the largest ``dat_freq`` of the WHOLE
+        band: the shards of a sharded signal (whose rows are
+        ``local_dat_freq``) share one reference.  ValueError on an empty
+        ``dms``, a negative or non-finite DM, a ``ref_freq`` below a channel
+        frequency (negative delays) and a delay that does not fit in int32."""
+        dm = np.atleast_1d(np.asarray(to_value(dms, 'pc/cm^3'), dtype=np.float64))
+        if dm.ndim != 1 or dm.size < 1:
+            raise ValueError("dedisperse: dms is empty or not one-dimensional")
+        if not np.all(np.isfinite(dm)) or np.any(dm < 0):
+            raise ValueError("dedisperse: a DM is negative or not finite")
+        f_all = np.asarray(to_value(signal.dat_freq, 'MHz'), dtype=np.float64)
+        f = np.asarray(to_value(getattr(signal, "local_dat_freq", signal.dat_freq), 'MHz'), dtype=np.float64)
+        fref = float(np.max(f_all)) if ref_freq is None else float(to_value(ref_freq, 'MHz'))
+        if not np.isfinite(fref) or fref <= 0 or np.any(f <= 0):
+            raise ValueError("dedisperse: frequencies must be positive and finite")
+        if np.any(f > fref):
+            raise ValueError("dedisperse: ref_freq %r MHz is below a channel frequency (negative delays)" % fref)
+        fs_hz = float(to_value(signal.samprate, 'MHz')) * 1e6
+        x = DM_K_VALUE * dm[:, None] * (np.power(f, -2.0) - fref ** -2.0)[None, :] * fs_hz
+        d = np.floor(x + 0.5)
+        if not np.all(np.isfinite(d)) or d.max() > np.iinfo(np.int32).max:
+            raise ValueError("dedisperse: a delay does not fit in int32")
+        return d.astype(np.int32)
+
+    @staticmethod
+    def _dedisperse_plan(signal, dms, ref_freq=None):
+        """Validate the arguments of :meth:`dedisperse` on the host (nothing
+        touches the device): returns (dms, delays, ref_freq, max_delay, C, N)."""
+        if getattr(signal, "sigtype", None) != "FilterBankSignal":
+            raise ValueError("dedisperse takes a FilterBankSignal, not %s"
+                             % getattr(signal, "sigtype", type(signal).__name__))
+        if signal.fold:
+            raise ValueError("dedisperse takes a search-mode signal (fold=False): a fold-mode buffer is tiled "
+                             "sub-integrations, not a time series")
+        if signal._buf is None and signal._pending is None:
+            raise ValueError("signal has no data: call Pulsar.make_pulses first")
+        dm = np.atleast_1d(np.asarray(to_value(dms, 'pc/cm^3'), dtype=np.float64))
+        delays = Backend.dedisperse_delays(signal, dm, ref_freq)
+        fref = (float(np.max(np.asarray(to_value(signal.dat_freq, 'MHz'), dtype=np.float64)))
+                if ref_freq is None else float(to_value(ref_freq, 'MHz')))
+        C, N = delays.shape[1], int(signal._ncols)
+        max_delay = int(delays.max())
+        if max_delay >= N:
+            raise ValueError("dedisperse: the largest delay (%d samples) leaves no output sample of %d"
+                             % (max_delay, N))
+        return dm, delays, fref, max_delay, C, N
+
+    def dedisperse(self, signal, dms, ref_freq=None):
+        """Incoherent dedispersion over the trial DMs ``dms`` on the device
+        (extension: the reference has no counterpart): the DM-time plane
+
+            plane[j][t] = sum_c data[c][t + d[j][c]],   t < T = N - max(d)
+
+        of a search-mode FilterBankSignal -- from ``make_pulses`` /
+        ``ISM.disperse`` / ``observe`` or from :meth:`channelize` -- with
+        d = :meth:`dedisperse_delays` (signal, dms, ref_freq).  One kernel
+        (``pss_dedisperse``), the exact direct sum in a fixed order, no host
+        copy of the data.  For a sharded signal the result is this rank's
+        partial sum over its channels.  Returns a :class:`DedispersedPlane`."""
+        dm, delays, fref, max_delay, C, N = self._dedisperse_plan(signal, dms, ref_freq)
+        data = signal.data                                    # flushes pending stages
+        if data.shape[0] != C:
+            raise ValueError("dedisperse: %d data rows for %d channel frequencies" % (data.shape[0], C))
+        tab = _engine.to_dev(delays)
+        T = N - max_delay
+        # rows on the 16-B grid, as channelize's: what reads the plane next can load 16 B
+        ld_out = (T + 3) // 4 * 4
+        out = torch.empty((delays.shape[0], ld_out), dtype=torch.float32, device=data.device)[:, :T]
+        rc = _lib.lib().pss_dedisperse(_engine.ptr(data), C, N, max(int(data.stride(0)), N), _engine.ptr(tab),
+                                       delays.shape[0], max_delay, _engine.ptr(out), ld_out, _engine.stream_ptr())
+        _lib.check(rc, "dedisperse")
+        return DedispersedPlane(out, dm, delays, signal._samprate_MHz(), fref, max_delay)
 
     def fold(self, signal, pulsar):
         """backend.py:34-49: Npbins = int(P * 2 * signal.samprate);
