@@ -406,6 +406,41 @@ int pss_normal_add(float *rows, int32_t nrows, int64_t n, int64_t ld, float scal
 int pss_dedisperse(const float *data, int32_t nchan, int64_t n, int64_t ld, const int32_t *delays,
                    int32_t ndm, int32_t max_delay, float *out, int64_t out_ld, void *stream);
 
+/*
+ * Single-pulse search of a DM-time plane (extension, no reference
+ * counterpart): a boxcar matched filter over the widths 2^k, k < nw, of
+ * plane[ndm][ld] float32 (T samples per row), normalised per trial by the
+ * device arrays mean[ndm] / rstd[ndm] and reduced to one result per cell of
+ * `cell` start times, nq = ceil(T / cell) cells per trial.  All arithmetic is
+ * IEEE float32, every line one rounded operation:
+ *   y[t]       = plane[j * ld + t] - mean[j]                      t < T
+ *   S_0[t]     = y[t]
+ *   S_{k+1}[t] = S_k[t] + S_k[t + 2^k]                            t + 2^(k+1) <= T
+ *   c[j][k]    = a_k * rstd[j],  a_k = 2^-ceil(k/2) * (k odd ? 0x3FB504F3 : 1)
+ *   z_k[t]     = S_k[t] * c[j][k]                                 k < nw, t + 2^k <= T
+ *   cell q     : the lexicographic maximum of (z, -k, -t) over all (k, t) with
+ *                q * cell <= t < min((q + 1) * cell, T) and t + 2^k <= T:
+ *                the largest z; ties go to the narrower width, then to the
+ *                earlier time; a NaN z never wins
+ *   snr[j * out_ld + q]  = that z, -inf if no candidate was greater than -inf
+ *   code[j * out_ld + q] = (k << 16) | (t - q * cell), 0 with a -inf result
+ * a_k is 2^(-k/2) (0x3FB504F3 is float32(sqrt 2)), so z is the box sum in
+ * units of its own standard deviation when rstd = 1 / sigma.  The balanced
+ * tree is part of the contract (prefix-sum differences round differently): the
+ * bits depend on neither the tile, the alignment of plane / ld / out_ld nor
+ * the run.  Widths with 2^k > T do not exist.  A candidate is valid by its
+ * index alone: no read leaves [0, T) of its row, and nothing is written
+ * outside snr / code [j * out_ld + 0 .. nq).  A workgroup owns 2048 start
+ * times of one trial and reads them and 2^(nw-1) - 1 samples of halo (rounded
+ * up to 256) once; no atomics, no workspace.
+ * PSS_EINVAL (nothing launched) on a NULL pointer, ndm < 1, T < 1, ld < T,
+ * nw outside [1, 13], cell not a power of two in [16, 2048], out_ld < nq,
+ * and when ceil(T / 2048) * ndm exceeds 2^31 - 1 (the launch grid).
+ */
+int pss_boxcar_search(const float *plane, int32_t ndm, int64_t T, int64_t ld, const float *mean,
+                      const float *rstd, int32_t nw, int32_t cell, float *snr, int32_t *code,
+                      int64_t out_ld, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,7 +19,7 @@ ROOT = os.path.dirname(HERE)
 # instantiated per unit), compiled in parallel and linked with the host code
 UNITS = ["pss_pipeline.hip", "pss_fourstep.hip", "pss_fourstep_b.hip", "pss_smooth.hip", "pss_smooth_b.hip",
          "pss_smooth_c.hip", "pss_single.hip", "pss_fallback.hip", "pss_searchout.hip", "pss_channelize.hip",
-         "pss_dedisperse.hip"]
+         "pss_dedisperse.hip", "pss_boxsearch.hip"]
 SRC = [os.path.join(HERE, "csrc", u) for u in UNITS] + [os.path.join(HERE, "csrc", "pss_host.cpp")]
 DEPS = SRC + [os.path.join(HERE, "csrc", f) for f in ("pss_engine.hpp", "pss_device.hpp", "pss_fft.hpp")] + \
     [os.path.join(ROOT, "include", "pss_hip.h")]

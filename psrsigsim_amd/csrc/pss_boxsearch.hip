@@ -1,0 +1,330 @@
+// pss_boxsearch.hip -- single-pulse search of the DM-time plane (extension, no
+// reference counterpart): a boxcar matched filter over the widths 2^k, k < nw,
+// normalised per trial and reduced to one (S/N, width, time) per cell of `cell`
+// start times.  The definition (include/pss_hip.h: pss_boxcar_search), all in
+// IEEE float32, one rounding per line:
+//
+//   y[t]       = plane[j][t] - mean[j]
+//   S_0        = y,   S_{k+1}[t] = S_k[t] + S_k[t + 2^k]        (balanced tree)
+//   z_k[t]     = S_k[t] * (a_k * rstd[j]),   a_k = 2^(-k/2)
+//   cell q     : lexicographic maximum of (z, -k, -t) over q cell <= t < (q+1) cell,
+//                t + 2^k <= T.
+//
+//   k_boxcar_search<HB, VEC> : a workgroup of 256 threads owns kBsTile = 2048 start
+//       times of one trial.  Lanes run along time: thread i holds the samples
+//       t0 + i + 256 m, m < NI = 8 + HB, in registers -- its 8 own start times
+//       and HB blocks of halo, 256 HB >= 2^(nw-1) - 1 (HB = 1 for nw <= 9, then
+//       2, 4, 8, 16 for nw = 10 .. 13).  The row's window is staged in LDS once
+//       (16-B loads when the row is on the 16-B grid, VEC, all issued before the
+//       first LDS store; element loads otherwise -- the same values), the mean
+//       subtracted as it is stored.  A level whose step 2^k is below 256 takes
+//       its partner S_k[t + 2^k] from LDS (the level written there by every
+//       thread, consecutive lanes on consecutive dwords: conflict-free); from
+//       2^k = 256 on the partner is the thread's own register m + 2^k / 256 and
+//       the levels need neither LDS nor a barrier.  That is the lever taken
+//       against the halo: at nw = 13 the halo triples the adds (24 registers for
+//       8 start times), but 4 of the 12 levels then cost one v_add per register
+//       and nothing else.
+//       Only the 8 own start times take the multiply and the compare; a sample
+//       at or past T is staged as 0 and a candidate is valid by its index
+//       (t + 2^k <= T), so no padding value ever reaches a result.  A thread
+//       keeps the best (z, k) of each of its start times (strict >, k rising:
+//       ties stay with the narrower width; a NaN never compares greater).
+//       The cells: (z, code) of the 2048 start times go to LDS, thread i scans
+//       the 8 consecutive times 8 i .. 8 i + 7 (one cell holds them all: cell is
+//       a multiple of 16), then cell / 8 neighbouring threads combine by a
+//       butterfly of wave shuffles (and, for cell >= 1024, across the waves
+//       through LDS) under the total order "larger z, then smaller code" --
+//       code = k << 16 | t - q cell, so a smaller code is the narrower width,
+//       then the earlier time.  One thread per cell stores snr and code as
+//       dwords; the cells of a tile are contiguous (cell <= 128: whole 64-B
+//       segments).  No atomics, no workspace; the bits depend on neither the
+//       alignment nor the launch geometry.
+//       Logical workgroup index = trial * tiles + tile, dealt to the XCDs in
+//       contiguous runs (as k_dedisperse): neighbouring tiles, which share a
+//       halo, read it through one L2.
+#include "pss_engine.hpp"
+
+using namespace pss;
+
+static constexpr int kBsThreads = 256;
+static constexpr int kBsOwn = 8;                          // start times per lane
+static constexpr int kBsTile = kBsThreads * kBsOwn;       // start times per workgroup
+static constexpr int kBsMaxW = 13;                        // widths 2^0 .. 2^12
+
+struct BsArgs {
+    int64_t T, ld, out_ld, nq, ntiles;
+    int32_t ndm, nw, cell, lcell;
+};
+
+// a_k = 2^-ceil(k/2) * (k odd ? fp32(sqrt 2) : 1): exact scalings of 0x3FB504F3
+__device__ __forceinline__ float bs_coef(int k) {
+    const float s = (k & 1) ? __uint_as_float(0x3FB504F3u) : 1.0f;
+    return s * __uint_as_float((uint32_t)(127 - ((k + 1) >> 1)) << 23);
+}
+
+// "a beats b": larger z, then the smaller code (narrower width, then earlier time)
+__device__ __forceinline__ bool bs_better(float za, int ca, float zb, int cb) {
+    return za > zb || (za == zb && ca < cb);
+}
+
+// y[e] = row[e] - mean for e < valid = min(256 NI, samples left in the row),
+// 0 for valid <= e < 256 (NI + 1) -> w[e]
+template <int NI, bool VEC>
+__device__ __forceinline__ void bs_stage(float *w, const float *row, int valid, float mean, int tid) {
+    constexpr int kAll = kBsThreads * (NI + 1);           // floats of the window
+    PSS_DASSERT(valid >= 1 && valid <= kBsThreads * NI);
+    const int ng = (valid + 3) >> 2;                      // 16-B groups that hold a sample
+    if (VEC && (valid & 3) == 0) {
+        // every group whole and inside the row (all but a row's last tiles):
+        // the loads of all passes are issued before the first LDS store waits
+        // for one (dd_stage).  Lanes past the last group re-load it (in
+        // bounds) and store zeros.
+        constexpr int NP = (kAll / 4 + kBsThreads - 1) / kBsThreads;
+        const float4 *src = reinterpret_cast<const float4 *>(row);
+        float4 v[NP];
+#pragma unroll
+        for (int i = 0; i < NP; ++i) v[i] = src[min(tid + i * kBsThreads, ng - 1)];
+#pragma unroll
+        for (int i = 0; i < NP; ++i) asm volatile("" : "+v"(v[i].x), "+v"(v[i].y), "+v"(v[i].z), "+v"(v[i].w));
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            const int g = tid + i * kBsThreads;
+            if (g < kAll / 4) {
+                float4 y = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                if (g < ng) {
+                    y.x = v[i].x - mean;
+                    y.y = v[i].y - mean;
+                    y.z = v[i].z - mean;
+                    y.w = v[i].w - mean;
+                }
+                *reinterpret_cast<float4 *>(w + 4 * g) = y;
+            }
+        }
+        return;
+    }
+    float x[NI + 1];
+#pragma unroll
+    for (int i = 0; i <= NI; ++i) {
+        const int e = tid + i * kBsThreads;
+        x[i] = e < valid ? row[e] : mean;
+    }
+#pragma unroll
+    for (int i = 0; i <= NI; ++i) {
+        const int e = tid + i * kBsThreads;
+        const float y = x[i] - mean;
+        w[e] = e < valid ? y : 0.0f;
+    }
+}
+
+template <int HB, bool VEC>
+__global__ __launch_bounds__(kBsThreads) void k_boxcar_search(const float *__restrict__ plane,
+                                                              const float *__restrict__ mean,
+                                                              const float *__restrict__ rstd,
+                                                              float *__restrict__ snr, int32_t *__restrict__ code,
+                                                              BsArgs a) {
+    constexpr int NI = kBsOwn + HB;                       // registers of samples per lane
+    // levels: HB == 1 serves every nw <= 9 (all steps below 256, nw at run
+    // time); a larger HB serves exactly one nw
+    constexpr int kNW = HB == 1 ? 9 : HB == 2 ? 10 : HB == 4 ? 11 : HB == 8 ? 12 : 13;
+    static_assert(kBsThreads * HB >= (1 << (kNW - 1)) - 1, "the halo blocks hold the widest box");
+    constexpr int kWin = kBsThreads * (NI + 1) > 2 * kBsTile ? kBsThreads * (NI + 1) : 2 * kBsTile;
+    __shared__ __align__(16) float win[kWin];
+    __shared__ float redz[kBsThreads / 64];
+    __shared__ int redc[kBsThreads / 64];
+    const int tid = threadIdx.x;
+    const int nw = HB == 1 ? a.nw : kNW;
+    PSS_DASSERT(a.nw >= 1 && a.nw <= kNW && (HB == 1 || a.nw == kNW));
+
+    // workgroup id -> (trial, tile), tiles fastest, through the XCD map of
+    // k_dedisperse.  Placement only changes the speed.
+    const unsigned total = gridDim.x, base = total >> 3, rem = total & 7u;
+    const unsigned xcd = blockIdx.x & 7u;
+    const unsigned lid = xcd * base + min(xcd, rem) + (blockIdx.x >> 3);
+    const int j = (int)(lid / (unsigned)a.ntiles);
+    const int64_t tile = (int64_t)(lid % (unsigned)a.ntiles);
+    const int64_t t0 = tile * kBsTile;
+    PSS_DASSERT(j >= 0 && j < a.ndm && t0 < a.T);
+    const float mu = mean[j];
+    const float rs = rstd[j];
+    const int64_t left = a.T - t0;                         // samples of the row from t0 on (>= 1)
+    // the window: NI blocks, which hold the tile's boxes (2048 + 2^(nw-1) - 1 samples)
+    const int valid = (int)min((int64_t)(kBsThreads * NI), left);
+    const int lim = (int)min((int64_t)(2 * kBsTile + (1 << kBsMaxW)), left);   // `left` in 32 bits
+
+    bs_stage<NI, VEC>(win, plane + (int64_t)j * a.ld + t0, valid, mu, tid);
+    __syncthreads();
+    float S[NI];
+#pragma unroll
+    for (int i = 0; i < NI; ++i) S[i] = win[tid + i * kBsThreads];
+
+    float bz[kBsOwn];
+    int bk[kBsOwn];
+#pragma unroll
+    for (int i = 0; i < kBsOwn; ++i) {
+        bz[i] = -INFINITY;
+        bk[i] = 0;
+    }
+#pragma unroll
+    for (int k = 0; k < kNW; ++k) {
+        if (k < nw) {                                      // (wave-uniform)
+            const float c = bs_coef(k) * rs;
+#pragma unroll
+            for (int i = 0; i < kBsOwn; ++i) {
+                const float z = S[i] * c;
+                // valid by index: the box [t, t + 2^k) inside [0, T)
+                const bool ok = tid + i * kBsThreads + (1 << k) <= lim;
+                if (ok && z > bz[i]) {
+                    bz[i] = z;
+                    bk[i] = k;
+                }
+            }
+            if (k + 1 < nw) {
+                constexpr int kStepMax = kBsThreads;
+                const int h = 1 << k;
+                if (h < kStepMax) {
+                    if (k > 0) {
+                        __syncthreads();                   // the previous level's reads are done
+#pragma unroll
+                        for (int i = 0; i < NI; ++i) win[tid + i * kBsThreads] = S[i];
+                        __syncthreads();
+                    }
+                    // (the last block's partners past the window's NI blocks are
+                    // the zero block: sums no valid candidate depends on)
+#pragma unroll
+                    for (int i = 0; i < NI; ++i) {
+                        PSS_DASSERT(tid + h + i * kBsThreads < kBsThreads * (NI + 1));
+                        const float b = win[tid + h + i * kBsThreads];
+                        S[i] = S[i] + b;
+                    }
+                } else {
+                    const int m = h / kStepMax;            // own registers, rising i: S[i + m] is still level k
+#pragma unroll
+                    for (int i = 0; i < NI; ++i)
+                        if (i + m < NI) S[i] = S[i] + S[i + m];
+                }
+            }
+        }
+    }
+
+    // per-cell reduction: (z, code) of the tile's start times through LDS
+    __syncthreads();
+    int *wcode = reinterpret_cast<int *>(win + kBsTile);
+    const int cmask = a.cell - 1;
+#pragma unroll
+    for (int i = 0; i < kBsOwn; ++i) {
+        const int e = tid + i * kBsThreads;
+        win[e] = bz[i];
+        wcode[e] = (bk[i] << 16) | (e & cmask);
+    }
+    __syncthreads();
+    float rz;
+    int rc;
+    {
+        const float4 z0 = *reinterpret_cast<const float4 *>(win + 8 * tid);
+        const float4 z1 = *reinterpret_cast<const float4 *>(win + 8 * tid + 4);
+        const int4 c0 = *reinterpret_cast<const int4 *>(wcode + 8 * tid);
+        const int4 c1 = *reinterpret_cast<const int4 *>(wcode + 8 * tid + 4);
+        const float zz[8] = {z0.x, z0.y, z0.z, z0.w, z1.x, z1.y, z1.z, z1.w};
+        const int cc[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
+        rz = zz[0];
+        rc = cc[0];
+#pragma unroll
+        for (int i = 1; i < 8; ++i)
+            if (bs_better(zz[i], cc[i], rz, rc)) {
+                rz = zz[i];
+                rc = cc[i];
+            }
+    }
+    const int tpc = a.cell >> 3;                           // threads per cell: 2 .. 256
+    for (int off = 1; off < min(tpc, 64); off <<= 1) {
+        const float oz = __shfl_xor(rz, off);
+        const int oc = __shfl_xor(rc, off);
+        if (bs_better(oz, oc, rz, rc)) {
+            rz = oz;
+            rc = oc;
+        }
+    }
+    int qc = tid >> (a.lcell - 3);                                  // the tile's cell of this thread
+    bool writer = (tid & (tpc - 1)) == 0;
+    if (tpc > 64) {                                        // (uniform) cell 1024 or 2048: across the waves
+        if ((tid & 63) == 0) {
+            redz[tid >> 6] = rz;
+            redc[tid >> 6] = rc;
+        }
+        __syncthreads();
+        const int wpc = tpc >> 6;                          // waves per cell: 2 or 4
+        writer = tid < kBsThreads / tpc;
+        qc = tid;
+        if (writer) {
+            rz = redz[tid * wpc];
+            rc = redc[tid * wpc];
+            for (int w = 1; w < wpc; ++w) {
+                const float oz = redz[tid * wpc + w];
+                const int oc = redc[tid * wpc + w];
+                if (bs_better(oz, oc, rz, rc)) {
+                    rz = oz;
+                    rc = oc;
+                }
+            }
+        }
+    }
+    const int64_t q = (t0 >> a.lcell) + qc;
+    if (writer && q < a.nq) {
+        PSS_DASSERT(q >= 0 && q < a.out_ld);
+        snr[(int64_t)j * a.out_ld + q] = rz;
+        code[(int64_t)j * a.out_ld + q] = rz == -INFINITY ? 0 : rc;
+    }
+}
+
+template <int HB>
+static int bs_launch(const float *plane, const float *mean, const float *rstd, float *snr, int32_t *code,
+                     const BsArgs &a, hipStream_t st) {
+    const dim3 grid((unsigned)(a.ntiles * a.ndm));
+    // 16-B loads of the window need the rows on the 16-B grid.  Same bits.
+    if ((uintptr_t)plane % 16 == 0 && a.ld % 4 == 0)
+        k_boxcar_search<HB, true><<<grid, dim3(kBsThreads), 0, st>>>(plane, mean, rstd, snr, code, a);
+    else
+        k_boxcar_search<HB, false><<<grid, dim3(kBsThreads), 0, st>>>(plane, mean, rstd, snr, code, a);
+    LAUNCHCHK();
+    return PSS_OK;
+}
+
+extern "C" {
+
+int pss_boxcar_search(const float *plane, int32_t ndm, int64_t T, int64_t ld, const float *mean, const float *rstd,
+                      int32_t nw, int32_t cell, float *snr, int32_t *code, int64_t out_ld, void *stream) {
+    if (!plane) return fail(PSS_EINVAL, "boxcar_search: plane is NULL");
+    if (!mean) return fail(PSS_EINVAL, "boxcar_search: mean is NULL");
+    if (!rstd) return fail(PSS_EINVAL, "boxcar_search: rstd is NULL");
+    if (!snr) return fail(PSS_EINVAL, "boxcar_search: snr is NULL");
+    if (!code) return fail(PSS_EINVAL, "boxcar_search: code is NULL");
+    if (ndm < 1) return fail(PSS_EINVAL, "boxcar_search: ndm %d < 1", ndm);
+    if (T < 1) return fail(PSS_EINVAL, "boxcar_search: T %lld < 1", (long long)T);
+    if (ld < T) return fail(PSS_EINVAL, "boxcar_search: ld %lld < T %lld", (long long)ld, (long long)T);
+    if (nw < 1 || nw > kBsMaxW) return fail(PSS_EINVAL, "boxcar_search: nw %d outside [1, %d]", nw, kBsMaxW);
+    if (cell < 16 || cell > kBsTile || (cell & (cell - 1)))
+        return fail(PSS_EINVAL, "boxcar_search: cell %d is not a power of two in [16, %d]", cell, kBsTile);
+    const int64_t nq = (T - 1) / cell + 1;
+    if (out_ld < nq) return fail(PSS_EINVAL, "boxcar_search: out_ld %lld < %lld cells", (long long)out_ld,
+                                 (long long)nq);
+    const int64_t ntiles = (T - 1) / kBsTile + 1;
+    if (ntiles > (int64_t)0x7fffffff / ndm)
+        return fail(PSS_EINVAL, "boxcar_search: %lld time tiles x %d trials exceed 2^31 - 1 workgroups",
+                    (long long)ntiles, ndm);
+    BsArgs a;
+    a.T = T; a.ld = ld; a.out_ld = out_ld; a.nq = nq; a.ntiles = ntiles;
+    a.ndm = ndm; a.nw = nw; a.cell = cell;
+    a.lcell = 0;
+    while ((1 << a.lcell) < cell) ++a.lcell;
+    hipStream_t st = (hipStream_t)stream;
+    switch (nw) {
+        case 13: return bs_launch<16>(plane, mean, rstd, snr, code, a, st);
+        case 12: return bs_launch<8>(plane, mean, rstd, snr, code, a, st);
+        case 11: return bs_launch<4>(plane, mean, rstd, snr, code, a, st);
+        case 10: return bs_launch<2>(plane, mean, rstd, snr, code, a, st);
+        default: return bs_launch<1>(plane, mean, rstd, snr, code, a, st);
+    }
+}
+
+}  // extern "C"

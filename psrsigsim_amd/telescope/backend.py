@@ -6,7 +6,7 @@ from .._units import make_quant, to_value
 from ..utils.constants import DM_K_VALUE
 from .. import _engine, _lib
 
-__all__ = ['Backend', 'DedispersedPlane']
+__all__ = ['Backend', 'DedispersedPlane', 'BoxcarPlane', 'PulseCandidates']
 
 
 class DedispersedPlane(object):
@@ -31,6 +31,146 @@ class DedispersedPlane(object):
     def __repr__(self):
         return "DedispersedPlane(%d trials x %d samples, ref %.6g MHz)" % (
             self.data.shape[0], self.data.shape[1], self.ref_freq)
+
+
+class BoxcarPlane(object):
+    """Result of :meth:`Backend.boxcar_snr`: the best boxcar of every cell of
+    ``cell`` start times of every trial, on the device (nq = ceil(T / cell)).
+
+    ``snr``        torch float32 [nDM, nq], -inf where a cell holds no candidate
+    ``time``       torch int64 [nDM, nq], start sample of the winning box
+    ``width_log2`` torch int32 [nDM, nq], its width is 2**width_log2 samples
+    ``code``       torch int32 [nDM, nq], the kernel's (k << 16) | (t - q * cell)
+    ``mean``       torch float64 [nDM], the baseline subtracted from each trial
+    ``std``        torch float64 [nDM], the noise of one sample of each trial
+                   (0: a trial without a usable variance, its S/N is 0)
+    ``cell``       start times per cell
+    ``plane``      the :class:`DedispersedPlane` that was searched"""
+
+    def __init__(self, snr, time, width_log2, code, mean, std, cell, plane):
+        self.snr = snr
+        self.time = time
+        self.width_log2 = width_log2
+        self.code = code
+        self.mean = mean
+        self.std = std
+        self.cell = cell
+        self.plane = plane
+
+    def __repr__(self):
+        return "BoxcarPlane(%d trials x %d cells of %d samples)" % (self.snr.shape[0], self.snr.shape[1], self.cell)
+
+
+CANDIDATE_DTYPE = np.dtype([("snr", np.float32), ("dm_index", np.int32), ("dm", np.float64), ("time", np.int64),
+                            ("width", np.int64), ("t_sec", np.float64), ("ncells", np.int64)])
+
+
+class PulseCandidates(object):
+    """Result of :meth:`Backend.single_pulse_search`: one candidate per cluster
+    of cells above the threshold, on the host, ordered by ``snr`` descending,
+    then (``dm_index``, ``time``, ``width``) ascending.
+
+    ``array`` is the NumPy structured array (``CANDIDATE_DTYPE``); every field
+    is also an attribute: ``snr``, ``dm_index``, ``dm`` (pc/cm^3), ``time``
+    (start sample), ``width`` (samples), ``t_sec`` (the box centre in seconds
+    at ``plane.ref_freq``) and ``ncells`` (cells of the cluster).  ``cells`` is
+    the :class:`BoxcarPlane` and ``threshold`` the S/N cut."""
+
+    def __init__(self, array, cells, threshold):
+        self.array = array
+        self.cells = cells
+        self.threshold = threshold
+
+    def __len__(self):
+        return len(self.array)
+
+    def __getitem__(self, i):
+        return self.array[i]
+
+    def __getattr__(self, name):
+        if name != "array" and name in CANDIDATE_DTYPE.names:
+            return self.array[name]
+        raise AttributeError(name)
+
+    def __repr__(self):
+        return "PulseCandidates(%d above S/N %g)" % (len(self.array), self.threshold)
+
+
+def cluster_cells(dm_index, time, width, dm_tol=1, time_tol=0):
+    """Friends-of-friends labels of the cells (``dm_index``, box ``[time,
+    time + width)``): a and b are friends iff ``|j_a - j_b| <= dm_tol`` and
+    ``max(t_a, t_b) - min(t_a + w_a, t_b + w_b) <= time_tol`` (at 0: boxes that
+    overlap or touch); clusters are the connected components.  Returns int64
+    labels, the smallest cell index of each cluster.
+
+    Sort-and-sweep with union-find, O(n (2 dm_tol + 1)): the cells are taken by
+    rising start time.  A later cell b is a friend of an earlier cell a of trial
+    j' iff ``t_b <= t_a + w_a + time_tol``, so of some cell of j' iff t_b is
+    within the trial's furthest reach so far -- and then of the cell a* that
+    reaches furthest, to which every other friend of b in j' is itself a friend
+    (both start by t_b and reach it).  Linking b to a* of each trial within
+    dm_tol therefore joins the same components as testing all pairs."""
+    j = np.asarray(dm_index, dtype=np.int64)
+    t = np.asarray(time, dtype=np.int64)
+    w = np.asarray(width, dtype=np.int64)
+    n = j.size
+    parent = list(range(n))
+
+    def find(a):
+        r = a
+        while parent[r] != r:
+            r = parent[r]
+        while parent[a] != r:
+            parent[a], a = r, parent[a]
+        return r
+
+    reach = {}                                      # trial -> (furthest end + tol so far, its cell)
+    order = np.argsort(t, kind="stable")
+    jl, tl, el = j.tolist(), t.tolist(), (t + w + int(time_tol)).tolist()
+    dmt = int(dm_tol)
+    for b in order.tolist():
+        jb, tb = jl[b], tl[b]
+        for jj in range(jb - dmt, jb + dmt + 1):
+            r = reach.get(jj)
+            if r is not None and tb <= r[0]:
+                ra, rb = find(r[1]), find(b)
+                if ra != rb:
+                    if ra < rb:
+                        parent[rb] = ra
+                    else:
+                        parent[ra] = rb
+        r = reach.get(jb)
+        if r is None or el[b] > r[0]:
+            reach[jb] = (el[b], b)
+    return np.array([find(a) for a in range(n)], dtype=np.int64)
+
+
+def candidates_from_cells(snr, dm_index, time, width, dms, samprate_MHz, dm_tol=1, time_tol=0):
+    """Cluster the cells (:func:`cluster_cells`) and return the structured
+    array of one candidate per cluster -- its lexicographic maximum of
+    (snr, -dm_index, -time) -- in the order of :class:`PulseCandidates`."""
+    snr = np.asarray(snr, dtype=np.float32)
+    j = np.asarray(dm_index, dtype=np.int64)
+    t = np.asarray(time, dtype=np.int64)
+    w = np.asarray(width, dtype=np.int64)
+    labels = cluster_cells(j, t, w, dm_tol, time_tol)
+    # best first within each label: snr descending, then dm_index, time ascending
+    order = np.lexsort((t, j, -snr.astype(np.float64), labels))
+    lab = labels[order]
+    first = np.ones(lab.size, dtype=bool)
+    first[1:] = lab[1:] != lab[:-1]
+    best = order[first]
+    count = np.diff(np.append(np.flatnonzero(first), lab.size))
+    out = np.empty(best.size, dtype=CANDIDATE_DTYPE)
+    out["snr"] = snr[best]
+    out["dm_index"] = j[best]
+    out["dm"] = np.asarray(dms, dtype=np.float64)[j[best]] if best.size else 0.0
+    out["time"] = t[best]
+    out["width"] = w[best]
+    out["t_sec"] = (t[best] + w[best] / 2.0) / (float(samprate_MHz) * 1e6)
+    out["ncells"] = count
+    final = np.lexsort((out["width"], out["time"], out["dm_index"], -out["snr"].astype(np.float64)))
+    return out[final]
 
 
 class Backend(object):
@@ -251,6 +391,159 @@ class Backend(object):
                                        delays.shape[0], max_delay, _engine.ptr(out), ld_out, _engine.stream_ptr())
         _lib.check(rc, "dedisperse")
         return DedispersedPlane(out, dm, delays, signal._samprate_MHz(), fref, max_delay)
+
+    @staticmethod
+    def _search_plan(plane, nwidths=8, cell=32, threshold=6.0, dm_tol=1, time_tol=0, max_cells=1 << 20,
+                     mean=None, std=None, stat_block=1024):
+        """Validate the arguments of :meth:`boxcar_snr` and
+        :meth:`single_pulse_search` on the host (nothing touches the device):
+        returns (nDM, T, nwidths, cell, threshold, dm_tol, time_tol, max_cells,
+        mean, std, stat_block), ``mean`` / ``std`` float64 [nDM] or None."""
+        if not isinstance(plane, DedispersedPlane):
+            raise ValueError("single-pulse search takes a DedispersedPlane, not %s" % type(plane).__name__)
+        ndm, T = int(plane.data.shape[0]), int(plane.data.shape[1])
+        if ndm < 1 or T < 1:
+            raise ValueError("single-pulse search: the plane is empty (%d trials x %d samples)" % (ndm, T))
+        try:
+            nw, ce, sb, mc = int(nwidths), int(cell), int(stat_block), int(max_cells)
+            ok = nw == nwidths and ce == cell and sb == stat_block and mc == max_cells
+        except (TypeError, ValueError, OverflowError):
+            ok = False
+        if not ok:
+            raise ValueError("single-pulse search: nwidths, cell, stat_block and max_cells are integers")
+        if nw < 1 or nw > 13:
+            raise ValueError("single-pulse search: nwidths %d outside [1, 13]" % nw)
+        if ce < 16 or ce > 2048 or (ce & (ce - 1)):
+            raise ValueError("single-pulse search: cell %d is not a power of two in [16, 2048]" % ce)
+        if sb < 2:
+            raise ValueError("single-pulse search: stat_block %d < 2" % sb)
+        if mc < 0:
+            raise ValueError("single-pulse search: max_cells %d < 0" % mc)
+        th = float(threshold)
+        if not np.isfinite(th) or th <= 0:
+            raise ValueError("single-pulse search: threshold %r is not finite and positive" % (threshold,))
+        if not (dm_tol >= 0) or not (time_tol >= 0):
+            raise ValueError("single-pulse search: dm_tol %r and time_tol %r must not be negative"
+                             % (dm_tol, time_tol))
+        if (mean is None) != (std is None):
+            raise ValueError("single-pulse search: give both mean and std, or neither")
+        if mean is not None:
+            stats = []
+            for name, v in (("mean", mean), ("std", std)):
+                a = np.asarray(v, dtype=np.float64)
+                if a.ndim == 0:
+                    a = np.full(ndm, float(a))
+                if a.ndim != 1 or a.size != ndm:
+                    raise ValueError("single-pulse search: %s has %s entries for %d trials"
+                                     % (name, "x".join(str(s) for s in a.shape), ndm))
+                if not np.all(np.isfinite(a)):
+                    raise ValueError("single-pulse search: %s has an entry that is not finite" % name)
+                stats.append(a)
+            mean, std = stats
+            if np.any(std <= 0):
+                raise ValueError("single-pulse search: std has an entry <= 0")
+        return ndm, T, nw, ce, th, dm_tol, time_tol, mc, mean, std, sb
+
+    @staticmethod
+    def _trial_stats(data, ld, stat_block):
+        """Robust per-trial statistics on the device, no host synchronisation:
+        ``pss_chan_stats`` over whole blocks of sb = min(stat_block, T) samples
+        (trailing samples do not enter), per block m = sum / sb and
+        v = sumsq / sb - m^2 in float64, and per trial the lower median (sorted
+        index (nb - 1) // 2) of each over its nb blocks -- a block that holds a
+        pulse does not move a median.  Returns (mean, var) float64 [nDM]."""
+        ndm, T = int(data.shape[0]), int(data.shape[1])
+        sb = min(int(stat_block), T)
+        nb = T // sb
+        s1 = torch.empty((nb, ndm), dtype=torch.float64, device=data.device)
+        s2 = torch.empty_like(s1)
+        mn = torch.empty((nb, ndm), dtype=torch.float32, device=data.device)
+        mx = torch.empty_like(mn)
+        # (at most 65535 trials a call: pss_chan_stats says so beyond)
+        _lib.check(_lib.lib().pss_chan_stats(_engine.ptr(data), ndm, ld, sb, nb, _engine.ptr(mn), _engine.ptr(mx),
+                                             _engine.ptr(s1), _engine.ptr(s2), _engine.stream_ptr()), "chan_stats")
+        m = s1 / sb
+        v = s2 / sb - m * m
+        mid = (nb - 1) // 2
+        return torch.sort(m, dim=0).values[mid], torch.sort(v, dim=0).values[mid]
+
+    def boxcar_snr(self, plane, nwidths=8, cell=32, mean=None, std=None, stat_block=1024):
+        """Boxcar matched filter of a DM-time plane on the device (extension:
+        the reference has no counterpart).  For every trial j and every box
+        [t, t + 2^k), k < ``nwidths``, inside the series,
+
+            z = (sum of (plane[j] - mean[j]) over the box) * 2^(-k/2) / std[j]
+
+        in float32 with the balanced summation tree of ``pss_boxcar_search``
+        (include/pss_hip.h), and per cell of ``cell`` (a power of two in
+        [16, 2048]) start times the largest z -- ties to the narrower box, then
+        the earlier time.  One kernel reads the plane once; only the
+        [nDM, ceil(T / cell)] map is written.  Returns a :class:`BoxcarPlane`.
+
+        ``mean`` / ``std`` (both or neither; scalars or array-likes of length
+        nDM) are the per-trial baseline and noise.  Left out, they are measured
+        on the device (``pss_chan_stats`` and torch float64, no host
+        synchronisation): the lower medians over blocks of ``stat_block``
+        samples of the block means and block variances, which a block holding a
+        pulse does not move (at most 65535 trials a call).  A trial whose
+        variance is not positive and finite gets S/N 0 everywhere."""
+        ndm, T, nw, ce, _, _, _, _, mean, std, sb = self._search_plan(
+            plane, nwidths=nwidths, cell=cell, mean=mean, std=std, stat_block=stat_block)
+        data = plane.data
+        if data.dtype != torch.float32 or data.stride(1) != 1:
+            data = data.to(torch.float32).contiguous()
+        ld = max(int(data.stride(0)), T)
+        if mean is not None:
+            mean32 = _engine.to_dev(mean.astype(np.float32))
+            rstd32 = _engine.to_dev((1.0 / std).astype(np.float32))
+            mean_d, std_d = _engine.to_dev(mean), _engine.to_dev(std)
+        else:
+            mean_d, var = self._trial_stats(data, ld, sb)
+            good = torch.isfinite(var) & (var > 0)
+            std_d = torch.where(good, torch.sqrt(var), torch.zeros_like(var))
+            mean32 = mean_d.to(torch.float32)
+            rstd32 = torch.where(good, 1.0 / torch.sqrt(var), torch.zeros_like(var)).to(torch.float32)
+        nq = (T + ce - 1) // ce
+        # rows of whole 64-B segments
+        out_ld = (nq + 15) // 16 * 16
+        snr = torch.empty((ndm, out_ld), dtype=torch.float32, device=data.device)[:, :nq]
+        code = torch.empty((ndm, out_ld), dtype=torch.int32, device=data.device)[:, :nq]
+        rc = _lib.lib().pss_boxcar_search(_engine.ptr(data), ndm, T, ld, _engine.ptr(mean32), _engine.ptr(rstd32),
+                                          nw, ce, _engine.ptr(snr), _engine.ptr(code), out_ld,
+                                          _engine.stream_ptr())
+        _lib.check(rc, "boxcar_search")
+        q0 = torch.arange(nq, dtype=torch.int64, device=data.device) * ce
+        time = q0[None, :] + (code & 0xFFFF).to(torch.int64)
+        return BoxcarPlane(snr, time, code >> 16, code, mean_d, std_d, ce, plane)
+
+    def single_pulse_search(self, plane, threshold=6.0, nwidths=8, cell=32, dm_tol=1, time_tol=0,
+                            max_cells=1 << 20, mean=None, std=None, stat_block=1024):
+        """Single-pulse search of a DM-time plane (extension: the reference has
+        no counterpart): :meth:`boxcar_snr`, then the cells with
+        ``snr >= threshold`` -- found on the device, only they cross to the
+        host -- clustered friends-of-friends into candidates.
+
+        Cells a and b (trial j, box [t, t + w)) are friends iff
+        ``|j_a - j_b| <= dm_tol`` and ``max(t_a, t_b) - min(t_a + w_a,
+        t_b + w_b) <= time_tol`` (at 0: boxes that overlap or touch); a cluster
+        is a connected component and its candidate the cell that is the
+        lexicographic maximum of (snr, -dm_index, -time).  More than
+        ``max_cells`` cells above the threshold raise ValueError.  Returns
+        :class:`PulseCandidates`."""
+        _, _, nw, ce, th, dm_tol, time_tol, mc, mean, std, sb = self._search_plan(
+            plane, nwidths, cell, threshold, dm_tol, time_tol, max_cells, mean, std, stat_block)
+        cells = self.boxcar_snr(plane, nwidths=nw, cell=ce, mean=mean, std=std, stat_block=sb)
+        idx = torch.nonzero(cells.snr >= th)
+        n = int(idx.shape[0])
+        if n > mc:
+            raise ValueError("single_pulse_search: %d cells at or above threshold %g exceed max_cells %d -- raise "
+                             "the threshold" % (n, th, mc))
+        j, q = idx[:, 0], idx[:, 1]
+        packed = torch.stack((j, cells.time[j, q], cells.width_log2[j, q].to(torch.int64))).cpu().numpy()
+        s = cells.snr[j, q].cpu().numpy()
+        arr = candidates_from_cells(s, packed[0], packed[1], np.left_shift(1, packed[2]), plane.dms,
+                                    plane.samprate, dm_tol, time_tol)
+        return PulseCandidates(arr, cells, th)
 
     def fold(self, signal, pulsar):
         """backend.py:34-49: Npbins = int(P * 2 * signal.samprate);
