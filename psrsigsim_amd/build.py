@@ -6,6 +6,7 @@ not mtimes: a checkout or a copy to the GPU box can leave a stale binary
 newer than its sources), and ``_lib.load`` refuses a library whose hash does
 not match the sources next to it.
 """
+import glob
 import hashlib
 import os
 import re
@@ -21,8 +22,8 @@ UNITS = ["pss_pipeline.hip", "pss_fourstep.hip", "pss_fourstep_b.hip", "pss_smoo
          "pss_smooth_c.hip", "pss_single.hip", "pss_fallback.hip", "pss_searchout.hip", "pss_channelize.hip",
          "pss_dedisperse.hip", "pss_boxsearch.hip"]
 SRC = [os.path.join(HERE, "csrc", u) for u in UNITS] + [os.path.join(HERE, "csrc", "pss_host.cpp")]
-DEPS = SRC + [os.path.join(HERE, "csrc", f) for f in ("pss_engine.hpp", "pss_device.hpp", "pss_fft.hpp")] + \
-    [os.path.join(ROOT, "include", "pss_hip.h")]
+# every header of csrc/ is hashed (a new one cannot be forgotten)
+DEPS = SRC + sorted(glob.glob(os.path.join(HERE, "csrc", "*.hpp"))) + [os.path.join(ROOT, "include", "pss_hip.h")]
 OUT = os.path.join(HERE, "libpss_hip.so")
 OUT_DEBUG = os.path.join(HERE, "libpss_hip_debug.so")
 ARCH = os.environ.get("PSS_OFFLOAD_ARCH", "gfx950")

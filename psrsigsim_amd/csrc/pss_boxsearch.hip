@@ -43,7 +43,7 @@
 //       Logical workgroup index = trial * tiles + tile, dealt to the XCDs in
 //       contiguous runs (as k_dedisperse): neighbouring tiles, which share a
 //       halo, read it through one L2.
-#include "pss_engine.hpp"
+#include "pss_common.hpp"
 
 using namespace pss;
 
@@ -52,7 +52,7 @@ static constexpr int kBsOwn = 8;                          // start times per lan
 static constexpr int kBsTile = kBsThreads * kBsOwn;       // start times per workgroup
 static constexpr int kBsMaxW = 13;                        // widths 2^0 .. 2^12
 
-struct BsArgs {
+struct BoxArgs {
     int64_t T, ld, out_ld, nq, ntiles;
     int32_t ndm, nw, cell, lcell;
 };
@@ -122,7 +122,7 @@ __global__ __launch_bounds__(kBsThreads) void k_boxcar_search(const float *__res
                                                               const float *__restrict__ mean,
                                                               const float *__restrict__ rstd,
                                                               float *__restrict__ snr, int32_t *__restrict__ code,
-                                                              BsArgs a) {
+                                                              BoxArgs a) {
     constexpr int NI = kBsOwn + HB;                       // registers of samples per lane
     // levels: HB == 1 serves every nw <= 9 (all steps below 256, nw at run
     // time); a larger HB serves exactly one nw
@@ -136,11 +136,8 @@ __global__ __launch_bounds__(kBsThreads) void k_boxcar_search(const float *__res
     const int nw = HB == 1 ? a.nw : kNW;
     PSS_DASSERT(a.nw >= 1 && a.nw <= kNW && (HB == 1 || a.nw == kNW));
 
-    // workgroup id -> (trial, tile), tiles fastest, through the XCD map of
-    // k_dedisperse.  Placement only changes the speed.
-    const unsigned total = gridDim.x, base = total >> 3, rem = total & 7u;
-    const unsigned xcd = blockIdx.x & 7u;
-    const unsigned lid = xcd * base + min(xcd, rem) + (blockIdx.x >> 3);
+    // workgroup id -> (trial, tile), tiles fastest, through the XCD run map
+    const unsigned lid = xcd_run_id();
     const int j = (int)(lid / (unsigned)a.ntiles);
     const int64_t tile = (int64_t)(lid % (unsigned)a.ntiles);
     const int64_t t0 = tile * kBsTile;
@@ -279,10 +276,10 @@ __global__ __launch_bounds__(kBsThreads) void k_boxcar_search(const float *__res
 
 template <int HB>
 static int bs_launch(const float *plane, const float *mean, const float *rstd, float *snr, int32_t *code,
-                     const BsArgs &a, hipStream_t st) {
+                     const BoxArgs &a, hipStream_t st) {
     const dim3 grid((unsigned)(a.ntiles * a.ndm));
     // 16-B loads of the window need the rows on the 16-B grid.  Same bits.
-    if ((uintptr_t)plane % 16 == 0 && a.ld % 4 == 0)
+    if (on_grid16(plane, a.ld))
         k_boxcar_search<HB, true><<<grid, dim3(kBsThreads), 0, st>>>(plane, mean, rstd, snr, code, a);
     else
         k_boxcar_search<HB, false><<<grid, dim3(kBsThreads), 0, st>>>(plane, mean, rstd, snr, code, a);
@@ -312,7 +309,7 @@ int pss_boxcar_search(const float *plane, int32_t ndm, int64_t T, int64_t ld, co
     if (ntiles > (int64_t)0x7fffffff / ndm)
         return fail(PSS_EINVAL, "boxcar_search: %lld time tiles x %d trials exceed 2^31 - 1 workgroups",
                     (long long)ntiles, ndm);
-    BsArgs a;
+    BoxArgs a;
     a.T = T; a.ld = ld; a.out_ld = out_ld; a.nq = nq; a.ntiles = ntiles;
     a.ndm = ndm; a.nw = nw; a.cell = cell;
     a.lcell = 0;

@@ -34,7 +34,10 @@
 //       and no spectra-major intermediate exists.
 //   k_normal_add : rows[r][n] += scale * N(0, 1), the Philox Box-Muller normal
 //       of the amplitude pulses (normal_x4), keyed (seed, call id, row, n).
-#include "pss_engine.hpp"
+#include <algorithm>
+
+#include "pss_common.hpp"
+#include "pss_fft.hpp"
 
 using namespace pss;
 
@@ -254,8 +257,8 @@ static int launch_channelize(const ChanArgs &a0, hipStream_t st) {
     // decided separately: the 16-B loads need x, ld and h on the 16-B grid; the
     // 16-B stores (register accumulators only: the LDS-tile kernels store
     // dwords, 16 lanes along time) need out and out_ld there.  Same bits.
-    const bool vl = ((uintptr_t)a.x % 16 == 0) && a.ld % 4 == 0 && ((uintptr_t)a.h % 16 == 0);
-    const bool vs = ((uintptr_t)a.out % 16 == 0) && a.out_ld % 4 == 0;
+    const bool vl = on_grid16(a.x, a.ld) && ((uintptr_t)a.h % 16 == 0);
+    const bool vs = on_grid16(a.out, a.out_ld);
     if (vl) launch_channelize_vs<CH, true>(a, grid, vs, st);
     else launch_channelize_vs<CH, false>(a, grid, vs, st);
     LAUNCHCHK();
@@ -334,7 +337,7 @@ int pss_normal_add(float *rows, int32_t nrows, int64_t n, int64_t ld, float scal
     if (nrows <= 0 || n == 0) return PSS_OK;
     if (!rows) return fail(PSS_EINVAL, "normal_add: NULL argument");
     const dim3 g = stream_grid((n + 3) / 4, nrows);
-    if ((uintptr_t)rows % 16 == 0 && ld % 4 == 0)
+    if (on_grid16(rows, ld))
         k_normal_add<true><<<g, dim3(256), 0, (hipStream_t)stream>>>(rows, n, ld, scale, seed, call_id);
     else
         k_normal_add<false><<<g, dim3(256), 0, (hipStream_t)stream>>>(rows, n, ld, scale, seed, call_id);

@@ -34,7 +34,7 @@
 //       Logical workgroup index = time tile * (trial groups) + trial group,
 //       dealt to the XCDs in contiguous runs: the groups of one time tile run
 //       together on one XCD and share its rows in that L2.
-#include "pss_engine.hpp"
+#include "pss_common.hpp"
 
 using namespace pss;
 
@@ -43,15 +43,8 @@ static constexpr int kDdS = 8;                        // samples per lane and tr
 static constexpr int kTB = kDdThreads * kDdS;         // output times per workgroup
 static constexpr int kND = 8;                         // trials per workgroup
 // channels per barrier pair, and trials whose LDS reads are in flight together
-// (A/B builds: build.py --variant NAME -DPSS_DD_CB=n -DPSS_DD_NJ=n)
-#ifndef PSS_DD_CB
-#define PSS_DD_CB 2
-#endif
-#ifndef PSS_DD_NJ
-#define PSS_DD_NJ 2
-#endif
-static constexpr int kCB = PSS_DD_CB;
-static constexpr int kNJ = PSS_DD_NJ;
+static constexpr int kCB = 2;
+static constexpr int kNJ = 2;
 static constexpr int kWin = 2 * kTB;                  // staged window, floats per channel
 static_assert(kNJ * kTB <= kWin && kND % kNJ == 0, "the wide path's trials share the window");
 static constexpr int kSpread = kWin - kTB - 4;        // widest staged spread of a channel's delays
@@ -131,13 +124,9 @@ __global__ __launch_bounds__(kDdThreads) void k_dedisperse(const float *__restri
     __shared__ __align__(16) float win[kCB][kWin];
     const int tid = threadIdx.x;
     // Workgroup id -> (time tile, trial group), groups fastest, through the XCD
-    // map: ids are dealt to the 8 XCDs round-robin, so XCD x is given the
-    // contiguous run of logical ids [x base + min(x, rem), ..): the trial groups
-    // of one time tile then run on one XCD, side by side, and its L2 fetches
-    // each row once for all of them.  Placement only changes the speed.
-    const unsigned total = gridDim.x, base = total >> 3, rem = total & 7u;
-    const unsigned xcd = blockIdx.x & 7u;
-    const unsigned lid = xcd * base + min(xcd, rem) + (blockIdx.x >> 3);
+    // run map: the trial groups of one time tile then run on one XCD, side by
+    // side, and its L2 fetches each row once for all of them.
+    const unsigned lid = xcd_run_id();
     const int g = (int)(lid % (unsigned)a.ngroups);
     const int64_t t0 = (int64_t)(lid / (unsigned)a.ngroups) * kTB;
     const int j0 = g * kND;
@@ -239,7 +228,7 @@ int pss_dedisperse(const float *data, int32_t nchan, int64_t n, int64_t ld, cons
     a.ngroups = (int32_t)ngroups; a.out_ld = out_ld; a.T = T;
     const dim3 grid((unsigned)(ntiles * ngroups));
     // 16-B loads of the staged windows need the rows on the 16-B grid.  Same bits.
-    if ((uintptr_t)data % 16 == 0 && ld % 4 == 0)
+    if (on_grid16(data, ld))
         k_dedisperse<true><<<grid, dim3(kDdThreads), 0, (hipStream_t)stream>>>(data, delays, out, a);
     else
         k_dedisperse<false><<<grid, dim3(kDdThreads), 0, (hipStream_t)stream>>>(data, delays, out, a);

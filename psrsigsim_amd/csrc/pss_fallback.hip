@@ -1,10 +1,9 @@
 // pss_fallback.hip -- the other even lengths: direct DFT (N <= 8192), Bluestein
 // chirp-z (N > 8192), the float64 null refine of the packed paths, odd-N shift_t.
-#include "pss_engine.hpp"
+#include "pss_stages.hpp"
+#include "pss_fft.hpp"
 
 using namespace pss;
-
-int launch_box_row(const KP &k, float *row, hipStream_t st);   // pss_pipeline.hip
 
 // ---------------------------------------------------------------------------
 // path 3: direct DFT fallback for even N that are not handled above.

@@ -293,6 +293,31 @@ struct Lds {
 template <int... Rs>
 struct RList {};
 
+// Radix plans of the 2^m lengths (the synthesis paths' and the channeliser's).
+// Column plans: B*N1 = 8192 complex per workgroup, 512 threads, 16 per thread.
+// Inverse plans (..I) mirror the forward ones where registers carry over
+// (single pass, rows); column inverses start from LDS and reuse the forward plan.
+// Row plans: N2 = 8192 (1 row, 512 thr) or N2 <= 4096 (4096/N2 rows, 256 thr).
+using C16 = RList<16>;
+using C32F = RList<16, 2>;
+using C32I = RList<2, 16>;
+using C64F = RList<16, 4>;
+using C64I = RList<4, 16>;
+using C128F = RList<16, 8>;
+using C128I = RList<8, 16>;
+using C256 = RList<16, 16>;
+using C512F = RList<16, 16, 2>;
+using C512I = RList<2, 16, 16>;
+using C1kF = RList<16, 16, 4>;
+using C1kI = RList<4, 16, 16>;
+using C2kF = RList<16, 16, 8>;
+using C2kI = RList<8, 16, 16>;
+using C4k = RList<16, 16, 16>;
+using C8kF = RList<16, 8, 8, 8>;
+using C8kI = RList<8, 8, 8, 16>;
+using C16kF = RList<16, 16, 8, 8>;
+using C16kI = RList<8, 8, 16, 16>;
+
 // LDS byte addressing.  With the swizzled layout, a row pitch RS that is a
 // multiple of 16 complex and an LDS buffer aligned to 128 B, the positions a
 // Stockham scatter writes -- base + q (Ns = 1) or base + 16 q (Ns = 16) -- sit

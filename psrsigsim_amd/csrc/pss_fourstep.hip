@@ -1,9 +1,24 @@
 // pss_fourstep.hip -- the power-of-two four-step: the dispatch, C3's 2^22 (other
-// lengths: pss_fourstep_b.hip), the delayed-null mask-table kernels and fix-up.
-#include "pss_engine.hpp"
-#include <algorithm>
+// lengths: pss_fourstep_b.hip), the delayed-null mask-table kernels and fix-up,
+// and the side streams the mask table is built on.
+#include "pss_fourstep.hpp"
 
 using namespace pss;
+
+SideStreams *side_streams() {
+    static SideStreams g[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
+    SideStreams &x = g[dev];
+    if (!x.ok) {
+        for (int i = 0; i < 2; ++i)
+            if (hipStreamCreateWithFlags(&x.s[i], hipStreamNonBlocking) != hipSuccess) return nullptr;
+        for (int i = 0; i < 40; ++i)
+            if (hipEventCreateWithFlags(&x.ev[i], hipEventDisableTiming) != hipSuccess) return nullptr;
+        x.ok = true;
+    }
+    return &x;
+}
 
 // Per-channel null decisions for the four-step column pass C.  A pass-C
 // workgroup owns the B columns [n20, n20 + B) of every row n1 (samples

@@ -1,29 +1,10 @@
 #pragma once
-// pss_engine.hpp -- device code and launch templates of the MI355X engine (gfx950),
-// shared by the launch units (pss_pipeline.hip, pss_fourstep.hip, pss_smooth.hip,
-// pss_single.hip, pss_fallback.hip).
-//
-// One PssPipeline run = source -> [FFT delay ramp] -> [null] -> [noise] -> data.
-// See include/pss_hip.h for the ABI and DESIGN.md for the kernel/roofline
-// discussion.  Paths:
-//   * no delay stage           : k_elementwise          (1 HBM pass)
-//   * N = 2^m, 64 <= N <= 8192 : k_single<L>            (1 HBM pass, FFT in LDS)
-//   * N = 2^m, N >= 16384      : k_colA -> k_row -> k_colC  (four-step, 2 spills)
-//   * 2^m x {6..60} (smooth)   : mixed-radix four-step
-//   * other even N <= 8192     : direct DFT              (O(N^2) in LDS tiles)
-//   * other even N >  8192     : Bluestein chirp-z through a 2^m four-step
-#include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-#include <math.h>
-#include <type_traits>
-
-#include "pss_device.hpp"
+// pss_fourstep.hpp -- the four-step kernel templates and their launchers
+// (N = N1 x N2: column pass A, row pass, column pass C, two spills), for the
+// units that instantiate them: pss_fourstep*.hip (N = 2^m) and pss_smooth*.hip
+// (mixed radix).  A change here rebuilds those units only.
+#include "pss_stages.hpp"
 #include "pss_fft.hpp"
-#include "../../include/pss_hip.h"
-#include <algorithm>
 
 // Fixed product choices (each measured against its alternatives, DESIGN.md
 // sections 3 and 10; the rejected variants live in the git history):
@@ -41,829 +22,6 @@
 //   * the delayed-null mask table built on a side stream next to pass A, and
 //     applied by the compacted fix-up (k_null_fix_list) after pass C.
 static constexpr int kBC = 16, kTC = 1024;   // LDS-resident fast pass C block / threads (passC_fast)
-// 1024-point columns: the register-resident fast pass C at two workgroups per
-// CU (0: passC_fast, the A/B partner -- build.py --variant NAME -DPSS_PASSC_COLS16=0)
-#ifndef PSS_PASSC_COLS16
-#define PSS_PASSC_COLS16 1
-#endif
-static constexpr bool kPassCCols16 = PSS_PASSC_COLS16 != 0;
-
-using namespace pss;
-
-// ---------------------------------------------------------------------------
-// error reporting and opt-in per-kernel timing (defined in pss_pipeline.hip)
-// ---------------------------------------------------------------------------
-int fail(int code, const char *fmt, ...);
-
-#define HIPCHK(x)                                                              \
-    do {                                                                       \
-        hipError_t e_ = (x);                                                   \
-        if (e_ != hipSuccess)                                                  \
-            return fail(PSS_EHIP, "%s: %s", #x, hipGetErrorString(e_));        \
-    } while (0)
-
-#define LAUNCHCHK()                                                            \
-    do {                                                                       \
-        hipError_t e_ = hipGetLastError();                                     \
-        if (e_ != hipSuccess)                                                  \
-            return fail(PSS_EHIP, "launch failed: %s", hipGetErrorString(e_)); \
-    } while (0)
-
-enum { TK_ELEM = 0, TK_SINGLE, TK_COLA, TK_ROW, TK_COLC, TK_FALLBACK, TK_NULLFIX, TK_N };
-void tk_begin(int kind, hipStream_t st);
-void tk_end(hipStream_t st);
-// launch-plan log (pss_plan_collect): every launch path notes the kernels it
-// picked ("fourstep 1024x4096 A:fast R:pair_row C:fast N:fix_list"), so the
-// parity tests can assert which kernels produced the bits they check
-void plan_note(const char *fmt, ...);
-
-// ---------------------------------------------------------------------------
-// kernel parameters
-// ---------------------------------------------------------------------------
-struct KP {
-    PssPipeline p;
-    int64_t N;      // samples per row
-    int64_t N1;     // four-step: column length (1 for single-pass)
-    int64_t N2;     // four-step: row length    (N for single-pass)
-    float invN;
-    // four-step pair mode (two channels per complex row)
-    int npairs;
-    int poff;       // chan0 & 1: pairs are (even, odd) GLOBAL channels
-    cf *Yd;         // data pair spill    [npairs][N1][sp]
-    cf *Ym;         // node pair spill    [KCH/2][N1][N2] (mask table build)
-    const cf *Mspec;// mask spectrum      [N1][N2] (natural k2 per row k1)
-    // delayed-null mask table (four-step lengths; see k_mask_table)
-    int mtab;               // 1: mask decisions come from the table
-    int log2n;
-    const uint2 *mt_bits;   // [N/32] {nulled-for-every-f bits, f-dependent bits}
-    const uint32_t *mt_base;// [N/32] index of the word's first f-dependent position
-    const float *mt_coef;   // [n_f_dependent][KCH] root records of the f-dependent positions (root_hit)
-    const uint32_t *mbits;  // [nchan][N/32] per-channel null decisions (k_mask_bits)
-    int mbB;                // column-block width B of pass C (mbits layout)
-    const cf *rtab;         // [npairs][RFL][2] row-pass pair ramp factors {E, D} (k_pair_tab)
-    hipEvent_t mask_ready;  // mask table built on a side stream: wait before its first use (or NULL)
-    const uint32_t *wlist;  // delayed null: table words with a nulled position (any f)
-    const uint32_t *nwlist; // its length (device)
-    // single-workgroup kernel with a float64-refined delayed null: the
-    // inverse transform's (data, mask) pairs go to this [nchan][N] buffer
-    // (the packed paths' W1) instead of through the epilogue
-    cf *w1_out;
-    // shared-profile fast pass A: the pulse profile at every sample, in the
-    // pass's item order (k_prof_cols, PairCols::prof_cols)
-    const float4 *pcol;
-};
-// pair spill row pitch and per-pair stride (complex)
-__host__ __device__ __forceinline__ int64_t rpitch(const KP &k) { return k.N2; }
-__host__ __device__ __forceinline__ int64_t pstride(const KP &k) { return k.N1 * rpitch(k); }
-
-
-// ---------------------------------------------------------------------------
-// Delayed-null mask table.
-//
-// The reference shifts ONE box row (the same for every channel) by each
-// channel's total delay s_c and nulls where the result exceeds 1
-// (pulsar.py:306-330).  Write s = i + f (i integer, f in [0,1)).  For integer
-// sample offsets d the shift_t kernel, Nyquist rule included, satisfies
-// h_s(d) = h_f(d - i): the integer part is an exact circular roll, so
-//     mask_c[n] = M(p, f_c),  p = (n - i_c) mod N,
-// with M(p, f) = shift_t(box, f)[p] one function of (p, f) for all channels.
-// As a function of f, M(p, .) is a trigonometric polynomial of bandwidth
-// pi (bins |k| <= N/2), so a degree-11 Chebyshev interpolant in t = 2f - 1
-// from KCH = 12 node shifts is exact to ~1e-9 relative (tools: DESIGN.md §3).
-// Per position the table stores whether M > 1 for EVERY f (bound
-// c0 -+ sum|c_n|), for NO f, or -- for the ~2% of positions near box edges
-// where the answer depends on f -- the f values (as t) where the fp32
-// interpolant crosses 1, found once per position by the table build
-// (root_hit; the per-channel lookup is then two compares).  The node shifts are
-// KCH/2 pair rows through the same FFT engine, once per run; per channel
-// nothing but a table lookup remains (no per-channel mask FFT or spill).
-// ---------------------------------------------------------------------------
-static constexpr int KCH = 12;
-// floats per f-dependent position record (root_hit): 16 (64 B, aligned)
-static constexpr int KREC = 16;
-// PCHIP intervals the fast pass A keeps in LDS (two rows; 69.7 KB FFT buffer +
-// 12 KB still allows two 512-thread workgroups per CU).
-static constexpr int kFastNint = 376;
-// shared-profile fast pass A reads the per-run sample table (PairCols::prof_cols)
-#ifndef PSS_PCOL
-#define PSS_PCOL 1
-#endif
-static constexpr bool kPcol = PSS_PCOL != 0;
-
-// t = 2 f - 1 and i from the mask ramp word w = frac(s / N) 2^64 (N = 2^L)
-__device__ __forceinline__ void mask_split(uint64_t w, int L, uint32_t &ishift, float &t) {
-    ishift = (uint32_t)(w >> (64 - L));
-    const uint64_t fr = w << L;                         // f in 2^-64 units
-    t = fmaf((float)(uint32_t)(fr >> 40), 1.1920928955078125e-07f, -1.0f);   // 2 f - 1
-}
-
-// Clenshaw evaluation of the degree-11 Chebyshev interpolant at t (the mask
-// value M(p, f), t = 2 f - 1), fp32: the table build's root scan uses it
-__device__ __forceinline__ float cheb_eval_r(const float4 (&q)[3], float t) {
-    const float4 a = q[0], b = q[1], d = q[2];
-    const float cc[KCH] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, d.x, d.y, d.z, d.w};
-    const float t2 = 2.0f * t;
-    float b1 = 0.f, b2 = 0.f;
-#pragma unroll
-    for (int n = KCH - 1; n >= 1; --n) {
-        const float b0 = fmaf(t2, b1, cc[n] - b2);
-        b2 = b1;
-        b1 = b0;
-    }
-    return fmaf(t, b1, cc[0] - b2);
-}
-
-// Decision of an f-dependent position from its ROOT record (k_mask_table):
-// rec = {count, s0, r_1 .. r_10, -}: the fp32 Chebyshev value at t exceeds 1
-// iff s0 XOR (the number of roots r_i < t) is odd.  The roots are where
-// cheb_eval_r(c, .) > 1 flips, found by a 257-point scan of t in [-1, 1]
-// (24 bisection steps per flip) whose cells are CERTIFIED to hold no hidden
-// pair of flips (g = value - 1, D2 = max|g''| <= sum_n |c_n| n^2 (n^2 - 1) / 3
-// by Markov's bound on T_n'', fp32 evaluation error included): a cell whose
-// ends share a sign holds no root when min(|g(t_j)|, |g(t_j+1)|) > D2 h^2 / 8
-// (the chord-interpolation error bound), and one with a sign change holds
-// exactly one when the secant |g(t_j+1) - g(t_j)| / h exceeds D2 h (g' keeps
-// its sign; ~2 % of the f-dependent positions of C3's mask fail this and keep
-// coefficient records, measured with tools/mask_cert.py).  The rule then reproduces the direct
-// evaluation except within ~1e-8 of a flip, with one 16-B load and two
-// compares per position instead of 48 B of coefficients and a 12-term
-// Clenshaw sum; unused roots are +inf.  A position whose cells cannot all be
-// certified keeps its coefficients instead: rec = {-1, -, -, -, c_0 .. c_11},
-// evaluated directly.  `a` is the record's first float4.
-__device__ __forceinline__ bool root_hit(const float4 a, const float *rec, float t) {
-    if (a.x < 0.f) {                     // uncertified: the coefficient record
-        const float4 q[3] = {reinterpret_cast<const float4 *>(rec)[1], reinterpret_cast<const float4 *>(rec)[2],
-                             reinterpret_cast<const float4 *>(rec)[3]};
-        return cheb_eval_r(q, t) > 1.0f;
-    }
-    bool h = (a.y != 0.f) ^ (t > a.z) ^ (t > a.w);
-    if (a.x > 2.f) {                    // rare: more than two flips over f in [0, 1)
-        const float4 b = reinterpret_cast<const float4 *>(rec)[1], c = reinterpret_cast<const float4 *>(rec)[2];
-        h ^= (t > b.x) ^ (t > b.y) ^ (t > b.z) ^ (t > b.w) ^ (t > c.x) ^ (t > c.y) ^ (t > c.z) ^ (t > c.w);
-    }
-    return h;
-}
-
-// Null decision bits (bit i: sample n0 + i) for 4 consecutive samples of a
-// channel with mask split (ishift, t): a 4-bit window of the two table words
-// covering positions p0..p0+3 (mod N), branch-free; the Chebyshev evaluation
-// only where a position's decision depends on f (~2% of positions).
-__device__ __forceinline__ uint32_t mask_hits4(const KP &k, int64_t n0, uint32_t ishift, float t) {
-    const uint32_t nm = (uint32_t)k.N - 1u;
-    const uint32_t p0 = ((uint32_t)n0 - ishift) & nm;
-    const uint32_t w = p0 >> 5, w2 = (w + 1u) & (nm >> 5), sh = p0 & 31u;
-    const uint2 A = k.mt_bits[w], Bw = k.mt_bits[w2];
-    uint32_t r = (uint32_t)(((((uint64_t)Bw.x) << 32) | A.x) >> sh) & 15u;
-    const uint32_t amb = (uint32_t)(((((uint64_t)Bw.y) << 32) | A.y) >> sh) & 15u;
-    if (amb) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if ((amb >> i) & 1u) {
-                const uint32_t p = (p0 + (uint32_t)i) & nm, pw = p >> 5;
-                const uint32_t word = (pw == w) ? A.y : Bw.y;
-                const uint32_t idx = k.mt_base[pw] + (uint32_t)__popc(word & ((1u << (p & 31u)) - 1u));
-                const float *rec = k.mt_coef + (int64_t)idx * KREC;
-                const bool hit = root_hit(reinterpret_cast<const float4 *>(rec)[0], rec, t);
-                r = (r & ~(1u << i)) | ((uint32_t)hit << i);
-            }
-        }
-    }
-    return r;
-}
-
-// Null decisions of the RUN <= 32 contiguous samples n .. n + RUN - 1 of a
-// channel with mask split (is, t): a window of the two table words covering
-// them; the Chebyshev evaluation only at f-dependent positions (~2%).
-__device__ __forceinline__ uint32_t mask_run(const KP &k, uint32_t n, uint32_t is, float t, uint32_t RUN) {
-    const uint32_t nm = (uint32_t)k.N - 1u, wm = nm >> 5;
-    const uint32_t p0 = (n - is) & nm, w = p0 >> 5, w2 = (w + 1u) & wm, sh = p0 & 31u;
-    const uint2 A = k.mt_bits[w], Bw = k.mt_bits[w2];
-    const uint32_t msk = RUN >= 32u ? 0xffffffffu : ((1u << RUN) - 1u);
-    uint32_t r32 = (uint32_t)(((((uint64_t)Bw.x) << 32) | A.x) >> sh) & msk;
-    uint32_t amb = (uint32_t)(((((uint64_t)Bw.y) << 32) | A.y) >> sh) & msk;
-    if (!amb) return r32;
-    // Ambiguous positions cluster at pulse edges (a lane may hold ~20): take
-    // them four at a time so the coefficient loads of a group are in flight
-    // together instead of one exposed latency per position (the table bases
-    // of the two words are loaded once).
-    const uint32_t baseA = k.mt_base[w], baseB = k.mt_base[w2];
-    while (amb) {
-        uint32_t ii[4], idx[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            ii[u] = amb ? (uint32_t)__ffs(amb) - 1u : 32u;
-            amb &= amb - 1u;
-            const uint32_t p = (p0 + (ii[u] & 31u)) & nm;
-            const bool inA = (p >> 5) == w;
-            const uint32_t word = inA ? A.y : Bw.y;
-            idx[u] = (inA ? baseA : baseB) + (uint32_t)__popc(word & ((1u << (p & 31u)) - 1u));
-        }
-        float4 a[4];
-        const float *rec[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            rec[u] = k.mt_coef + (int64_t)(ii[u] < 32u ? idx[u] : idx[0]) * KREC;
-            a[u] = reinterpret_cast<const float4 *>(rec[u])[0];
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            if (ii[u] < 32u) {
-                const bool hit = root_hit(a[u], rec[u], t);
-                r32 = (r32 & ~(1u << ii[u])) | ((uint32_t)hit << ii[u]);
-            }
-        }
-    }
-    return r32;
-}
-
-// 4 null decisions of channel row r for samples n1 N2 + n20 + b4 .. + 3.
-// (column block blockIdx.x of B columns, N1 rows; B, N1 as in pass C)
-template <int B, int N1>
-__device__ __forceinline__ uint32_t mask_bits4(const KP &k, int r, int cbx, int n1, int b4) {
-    const uint32_t bp = (((uint32_t)cbx * (uint32_t)N1 + (uint32_t)n1) * (uint32_t)B) + (uint32_t)b4;
-    return (k.mbits[(int64_t)r * (k.N >> 5) + (bp >> 5)] >> (bp & 31u)) & 15u;
-}
-
-// XCD-aware block order of the column passes.  Workgroups are dispatched
-// round-robin over the 8 XCDs (linear id % 8), each with its own L2; the
-// passes touch B-column segments of every row (32 B of fp32 output per channel
-// for B = 8, a quarter of a 128-B line).  Remapping linear id ->
-// (id % 8) * (total / 8) + id / 8 gives each XCD a contiguous range of column
-// blocks, so the pieces of a line are written through the same L2 at about the
-// same time and merge there.  Measured (pass C, 2048 x 2^22): 17.8-19 ms with
-// the remap, 61 ms without, 58 ms with the blocks bit-reversed over the row;
-// contiguous (wrong-place) stores would take 14.3 ms -- the residual cost of
-// the strided output is ~4 ms.  Non-temporal / sc1 loads of the spill make it
-// worse (21-25 ms): neighbouring blocks share the spill's lines through L2.
-// compile-time loop: f(std::integral_constant<int, I>) for I in [B, E)
-template <int B, int E, typename F>
-__device__ __forceinline__ void static_for(F &&f) {
-    if constexpr (B < E) {
-        f(std::integral_constant<int, B>{});
-        static_for<B + 1, E>(f);
-    }
-}
-
-__device__ __forceinline__ void xcd_block(int &bx, int &by) {
-    const uint32_t gx = gridDim.x, total = gx * gridDim.y;
-    const uint32_t id = blockIdx.x + blockIdx.y * gx;
-    const uint32_t l = ((total & 7u) == 0u) ? (id & 7u) * (total >> 3) + (id >> 3) : id;
-    by = (int)(l / gx);
-    bx = (int)(l - (uint32_t)by * gx);
-}
-
-__device__ __forceinline__ int64_t floordiv(int64_t a, int64_t b) {
-    int64_t q = a / b;
-    if ((a % b != 0) && ((a < 0) != (b < 0))) --q;
-    return q;
-}
-
-// Box (nulled pulse) covering sample n, following the reference's numpy
-// indexing: bins = arange(Nph p, Nph (p+1)) + shift_val, filtered < N; negative
-// bins address from the end; later pulses in the choice list overwrite.
-__device__ __forceinline__ bool box_of(const KP &k, int64_t n, int &rank, int &j) {
-    const PssPipeline &p = k.p;
-    rank = -1;
-    const int64_t nph = p.nph;
-    const int64_t shift = p.null_shift_dev ? *p.null_shift_dev : p.null_shift;
-    int64_t q = n - shift;
-    int64_t s = floordiv(q, nph);
-    if (s >= 0 && s < p.null_slots) {
-        int r = p.null_rank[s];
-        if (r >= 0) { rank = r; j = (int)(q - s * nph); }
-    }
-    q = n - k.N - shift;                 // the same sample reached by a negative bin
-    s = floordiv(q, nph);
-    if (s >= 0 && s < p.null_slots) {
-        int r = p.null_rank[s];
-        if (r > rank) { rank = r; j = (int)(q - s * nph); }
-    }
-    return rank >= 0;
-}
-
-__device__ __forceinline__ float box_value(const KP &k, int64_t n, int rank, int j) {
-    const PssPipeline &p = k.p;
-    if (p.inj_box) return p.inj_box[n];
-    Rng g(p.seed, p.call_null, P_BOX);
-    return chi2_general(g, (uint32_t)j, (uint32_t)rank, p.null_box_df) * p.null_box_scale;
-}
-
-// chi2 draws for 4 consecutive samples n0..n0+3 (n0 % 4 == 0) of channel c.
-// df == 1: one Philox block per 4 samples; otherwise the Marsaglia-Tsang
-// pair sampler, one shared block per 2 samples (chi2_pair).
-__device__ __forceinline__ void draw4(const Rng &g, int64_t n0, uint32_t c, float df, float (&x)[4]) {
-    if (df == 1.0f) {
-        float4 q = chi2_1x4(g.bits((uint32_t)(n0 >> 2), c, (uint32_t)(n0 >> 34)));
-        x[0] = q.x; x[1] = q.y; x[2] = q.z; x[3] = q.w;
-    } else {
-        const uint32_t m = (uint32_t)(n0 >> 1);
-        chi2_pair(g, m, c, df, x[0], x[1]);
-        chi2_pair(g, m + 1u, c, df, x[2], x[3]);
-    }
-}
-
-// Interval index and fraction of sample n's pulse phase (shared by every
-// channel: only the coefficient row differs).
-__device__ __forceinline__ void pchip_locate(const KP &k, int64_t n, uint32_t &iv, float &u) {
-    const PssPipeline &p = k.p;
-    // ph = n * phase_step mod 2^64 (2^-64 cycles), n < 2^32: 32-bit products only
-    const uint32_t nn = (uint32_t)n;
-    const uint64_t ph = (uint64_t)nn * (uint32_t)p.phase_step +
-                        ((uint64_t)(nn * (uint32_t)(p.phase_step >> 32)) << 32);
-    // ph * M = iv 2^64 + fraction; u = (ph * M) >> 32 holds iv and fraction bits 32..63
-    const uint64_t t = (uint64_t)(uint32_t)ph * p.knot_m;
-    const uint64_t u64 = (uint64_t)(uint32_t)(ph >> 32) * p.knot_m + (t >> 32);
-    iv = (uint32_t)(u64 >> 32);                                    // interval index
-    u = frac23((uint32_t)u64);                                     // fraction, 23 bits
-    if (iv >= (uint32_t)p.nint) {                                  // extrapolate
-        u += (float)(iv - (uint32_t)(p.nint - 1));
-        iv = p.nint - 1;
-    }
-}
-
-// The same (interval, fraction) for consecutive samples by increments: the
-// 96-bit product A(n) = (n phase_step mod 2^64) * knot_m, kept as three
-// 32-bit words (hi = interval field, mid = fraction, lo = guard), advances by
-// D = phase_step * knot_m; when the phase wraps the interval field comes back
-// by knot_m.  Exact integer arithmetic: bitwise the values pchip_locate
-// computes, at one add-with-carry chain and a min per sample (the 64-bit form
-// compiled to nine VALU per step) instead of four 32 x 32 -> 64 multiplies.
-struct PhaseWalk {
-    uint32_t lo, mid, hi;
-    __device__ __forceinline__ void start(const PssPipeline &p, uint32_t n) {
-        const uint64_t ph = (uint64_t)n * (uint32_t)p.phase_step + ((uint64_t)(n * (uint32_t)(p.phase_step >> 32)) << 32);
-        const uint64_t t = (uint64_t)(uint32_t)ph * p.knot_m;
-        lo = (uint32_t)t;
-        const uint64_t u64 = (uint64_t)(uint32_t)(ph >> 32) * p.knot_m + (t >> 32);
-        mid = (uint32_t)u64;
-        hi = (uint32_t)(u64 >> 32);
-    }
-    __device__ __forceinline__ void step(uint32_t dlo, uint64_t dhi, uint32_t M) {
-        unsigned c;
-        lo = __builtin_addc(lo, dlo, 0u, &c);
-        mid = __builtin_addc(mid, (uint32_t)dhi, c, &c);
-        hi = hi + (uint32_t)(dhi >> 32) + c;
-        // (hi >= M) ? hi - M : hi -- hi < 2 M here, and for hi < M the
-        // difference wraps above hi (M <= 2^31)
-        hi = min(hi, hi - M);
-    }
-    __device__ __forceinline__ void get(const PssPipeline &p, uint32_t &iv, float &u) const {
-        iv = hi;
-        u = frac23(mid);
-        if (iv >= (uint32_t)p.nint) {
-            u += (float)(iv - (uint32_t)(p.nint - 1));
-            iv = p.nint - 1;
-        }
-    }
-    // the same for a table that spans the whole period (nint == knot_m, the
-    // host's extrapolated pieces appended: pulsar._device_table), where
-    // iv < knot_m needs no clamp -- bitwise what get() returns then
-    __device__ __forceinline__ void get_full(uint32_t &iv, float &u) const {
-        iv = hi;
-        u = frac23(mid);
-    }
-};
-__device__ __forceinline__ void phase_delta(const PssPipeline &p, uint32_t &dlo, uint64_t &dhi) {
-    const uint64_t t = (uint64_t)(uint32_t)p.phase_step * p.knot_m;
-    dlo = (uint32_t)t;
-    dhi = (uint64_t)(uint32_t)(p.phase_step >> 32) * p.knot_m + (t >> 32);
-}
-// ... for a walk in strides of S samples: D = (S phase_step mod 2^64) knot_m
-// (exact: the walk's sum stays below 2 knot_m in the interval field)
-__device__ __forceinline__ void phase_delta_n(const PssPipeline &p, uint64_t S, uint32_t &dlo, uint64_t &dhi) {
-    const uint64_t ps = p.phase_step * S;
-    const uint64_t t = (uint64_t)(uint32_t)ps * p.knot_m;
-    dlo = (uint32_t)t;
-    dhi = (uint64_t)(uint32_t)(ps >> 32) * p.knot_m + (t >> 32);
-}
-
-__device__ __forceinline__ float pchip_row(const KP &k, int prow, uint32_t iv, float u) {
-    float4 cc;
-    if (k.p.prof_split) {
-        // non-uniform knots: cell iv holds the cubics on either side of its
-        // one interior knot (both in the cell coordinate u)
-        const float4 *c = reinterpret_cast<const float4 *>(k.p.prof) + ((int64_t)prow * k.p.nint + iv) * 2;
-        const float s = k.p.prof[(int64_t)k.p.prof_rows * k.p.nint * 8 + iv];
-        cc = (u >= s) ? c[1] : c[0];
-    } else {
-        cc = reinterpret_cast<const float4 *>(k.p.prof)[(int64_t)prow * k.p.nint + iv];
-    }
-    return fmaf(fmaf(fmaf(cc.x, u, cc.y), u, cc.z), u, cc.w);
-}
-
-__device__ __forceinline__ float pchip_eval(const KP &k, int prow, int64_t n) {
-    uint32_t iv;
-    float u;
-    pchip_locate(k, n, iv, u);
-    return pchip_row(k, prow, iv, u);
-}
-
-// Analytic Gaussian portrait at sample n's pulse phase (amplitude pulses of
-// a GaussProfile / 1-D GaussPortrait, portraits.py:143-178, 277-290):
-// prof = [nint components][4] = {peak, 1/width, amp/Amax, 0}, channel
-// independent; the phase is pchip_locate's fraction with knot_m = 1.
-__device__ __forceinline__ float gauss_eval(const KP &k, int64_t n) {
-    uint32_t iv;
-    float u;
-    pchip_locate(k, n, iv, u);
-    const float4 *cp = reinterpret_cast<const float4 *>(k.p.prof);
-    float acc = 0.f;
-    for (int j = 0; j < k.p.nint; ++j) {
-        const float4 c = cp[j];
-        const float d = (u - c.x) * c.y;
-        acc = fmaf(c.z, __expf(-0.5f * d * d), acc);
-    }
-    return acc;
-}
-
-// Source stage for 4 consecutive samples (cnt valid) of local row r.
-// re = data (generated or loaded, with an undelayed null applied);
-// im = delayed-null box mask (0 elsewhere).
-__device__ __forceinline__ void source4(const KP &k, int r, int64_t n0, int cnt,
-                                        float (&re)[4], float (&im)[4], bool want_re,
-                                        bool want_im = true) {
-    const PssPipeline &p = k.p;
-    const uint32_t c = (uint32_t)(p.chan0 + r);
-    PSS_DASSERT(r >= 0 && r < p.nchan && n0 >= 0 && n0 + cnt <= k.N);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { re[i] = 0.f; im[i] = 0.f; }
-    if (want_re) {
-        if (p.src == PSS_SRC_LOAD) {
-            const float *row = p.data + (int64_t)r * p.ld;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) if (i < cnt) re[i] = row[n0 + i];
-        } else {
-            float x[4];
-            float dn = p.draw_norm;
-            if (p.inj_gen) {
-                const float *row = p.inj_gen + (int64_t)r * k.N;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) x[i] = (i < cnt) ? row[n0 + i] : 0.f;
-            } else if (p.gen_amp) {
-                Rng g(p.seed, p.call_gen, P_PULSE);
-                const float4 z = normal_x4(g.bits((uint32_t)(n0 >> 2), c, (uint32_t)(n0 >> 34)));
-                x[0] = z.x; x[1] = z.y; x[2] = z.z; x[3] = z.w;
-            } else if (p.gen_df == 1.0f) {
-                // chi2(1) draws with draw_norm folded into the sampler (as the
-                // fast pass A draws them: bitwise the same values)
-                // (Philox block n >> 2 holds samples 4 (n >> 2) .. + 3 at every N)
-                Rng g(p.seed, p.call_gen, P_PULSE);
-                const float4 q = chi2_1x4(g.bits((uint32_t)(n0 >> 2), c, (uint32_t)(n0 >> 34)), p.draw_norm);
-                x[0] = q.x; x[1] = q.y; x[2] = q.z; x[3] = q.w;
-                dn = 1.0f;                                   // (x * 1 is exact)
-            } else {
-                Rng g(p.seed, p.call_gen, P_PULSE);
-                draw4(g, n0, c, p.gen_df, x);
-            }
-            const int prow = (p.prof_rows == 1) ? 0 : (int)c - p.prof_row0;
-            if (p.src == PSS_SRC_SEARCH && p.gen_amp) {
-                // amplitude pulses: sqrt(calc_profiles(phase)) x N(0, 1)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    if (i < cnt) {
-                        const float pr = (p.gen_amp == 2) ? gauss_eval(k, n0 + i) : pchip_eval(k, prow, n0 + i);
-                        re[i] = sqrtf(fmaxf(pr, 0.0f)) * x[i] * dn;
-                    }
-                }
-            } else if (p.src == PSS_SRC_SEARCH) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    if (i < cnt) re[i] = pchip_eval(k, prow, n0 + i) * x[i] * dn;
-            } else {   // FOLD
-                const float *pr = p.prof + (int64_t)prow * p.nph;
-                uint32_t b = (uint32_t)(n0 % p.nph);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    if (i < cnt) re[i] = pr[b] * x[i] * dn;
-                    if (++b == (uint32_t)p.nph) b = 0;
-                }
-            }
-        }
-        if (p.null_mode == PSS_NULL_UNDELAYED) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                int rk, j;
-                if (i < cnt && box_of(k, n0 + i, rk, j)) re[i] = box_value(k, n0 + i, rk, j);
-            }
-        }
-    }
-    if (want_im && p.null_mode == PSS_NULL_DELAYED) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            int rk, j;
-            if (i < cnt) {
-                if (p.inj_box) im[i] = p.inj_box[n0 + i];
-                else if (box_of(k, n0 + i, rk, j)) im[i] = box_value(k, n0 + i, rk, j);
-            }
-        }
-    }
-}
-
-// observe()'s resampled pre-noise copy (PssPipeline.out_len > 0): the
-// samples n0 .. n0 + cnt - 1 of row r added into the float64 sums of the
-// windows [lo_j, hi_j) that hold them (down_sample, utils.py:62-68: lo_j =
-// j f; rebin, utils.py:71-91: lo_j = ceil(j step), hi_j = ceil(j step + step)
-// clipped to N, so neighbouring windows may share a sample).  The edges are
-// recomputed from step with the host's float64 operations (out_lo / out_hi
-// serve the finalize kernel's counts); a window holding n is floor(n / step)
-// or the one before.  A lane's samples form a head piece (its first window)
-// and a tail piece (its last; pieces in between go straight to their
-// atomics); the head joins the previous lane's tail when they are the same
-// window, and the tails are summed over each run of lanes with the same
-// window -- a segmented reduction by doubling that only extends a sum over
-// lanes it has covered without a gap, and stops once no run is still
-// growing -- so one no-return float64 atomic leaves the wave per window
-// piece.  (Within-wave sums in fp32: at most 256 samples, summed as a tree.)
-// The atomics land in the hardware's order: the pieces are fp32 sums of one
-// row's samples, so their float64 sum is exact (order-free) unless a window
-// mixes pieces ~2^29 apart in magnitude, and a last-bit difference of the
-// float64 mean changes the float32 / int8 result only at a rounding boundary
-// (tests/test_gpu_observe_resample.py: two identical runs, the same bits).
-// Waves whose lanes hold different rows (the single-workgroup kernel's row
-// batches) skip the cross-lane step.  k_out_finalize divides, clips and casts
-// (telescope.py:140-145).  All active lanes of a wave call it together (the
-// epilogues' item loops are wave-uniform up to their tails; inactive lanes
-// are masked out through the ballot).
-__device__ __forceinline__ void out_windows(const PssPipeline &p, int r, uint32_t N, uint32_t n0, int cnt,
-                                            const float (&v)[4]) {
-    const int lane = (int)__lane_id();
-    const uint64_t act = __ballot(1);
-    const uint32_t L = (uint32_t)p.out_len;
-    const bool uniform = p.out_lo == nullptr;
-    const double step = p.out_step;
-    const uint32_t f = (uint32_t)step;
-    double *acc = p.out_acc + (int64_t)r * L;
-    const uint32_t last = n0 + (uint32_t)cnt - 1u;
-    int64_t ja, jb;
-    if (uniform) {
-        ja = n0 / f;
-        jb = last / f;
-    } else {
-        const double inv = 1.0 / step;      // (wave-uniform: hoisted by the compiler)
-        ja = (int64_t)floor((double)n0 * inv) - 2;
-        jb = (int64_t)floor((double)last * inv) + 1;
-    }
-    ja = ja < 0 ? 0 : ja;
-    jb = jb > (int64_t)L - 1 ? (int64_t)L - 1 : jb;
-    uint32_t jH = 0xffffffffu, jT = 0xffffffffu;      // head / tail window, ~0: none
-    float sH = 0.f, sT = 0.f;
-    for (int64_t jj = ja; jj <= jb; ++jj) {
-        const uint32_t j = (uint32_t)jj;
-        uint32_t lo, hi;
-        if (uniform) {
-            lo = j * f;
-            hi = lo + f;
-        } else {
-            // two statements: the sum is not contracted into an fma
-            const double lb = (double)j * step;
-            const double rb = lb + step;
-            lo = (uint32_t)ceil(lb);
-            hi = (uint32_t)ceil(rb);
-            hi = hi > N ? N : hi;
-        }
-        float s = 0.f;
-        bool any = false;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const uint32_t n = n0 + (uint32_t)i;
-            if (i < cnt && n >= lo && n < hi) {
-                s += v[i];
-                any = true;
-            }
-        }
-        if (!any) continue;
-        if (jT == 0xffffffffu) {
-            jH = jT = j;
-            sT = s;
-        } else {
-            if (jH == jT) sH = sT;                            // the first window becomes the head
-            else unsafeAtomicAdd(acc + jT, (double)sT);        // a window in the middle of the lane
-            jT = j;
-            sT = s;
-        }
-    }
-    const bool has_head = jT != 0xffffffffu && jH != jT;
-    const int r0 = __builtin_amdgcn_readfirstlane(r);
-    if (__ballot(r != r0) != 0ull) {
-        // lanes of several rows: no cross-lane merge
-        if (has_head) unsafeAtomicAdd(acc + jH, (double)sH);
-        if (jT != 0xffffffffu) unsafeAtomicAdd(acc + jT, (double)sT);
-        return;
-    }
-    // the head joins the previous lane's tail (the same window)
-    const uint32_t nxt_h = (uint32_t)__shfl_down((int)(has_head ? jH : 0xffffffffu), 1);
-    const float nxt_s = __shfl_down(sH, 1);
-    const uint32_t prv_t = (uint32_t)__shfl_up((int)jT, 1);
-    const bool nxt_ok = lane < 63 && ((act >> (lane + 1)) & 1ull);
-    const bool prv_ok = lane > 0 && ((act >> (lane - 1)) & 1ull);
-    if (jT != 0xffffffffu && nxt_ok && nxt_h == jT) sT += nxt_s;
-    if (has_head && !(prv_ok && prv_t == jH)) unsafeAtomicAdd(acc + jH, (double)sH);
-    // segmented sum of the tails over runs of lanes with one window
-    const uint32_t key = jT != 0xffffffffu ? jT : 0x80000000u + (uint32_t)lane;   // no tail: a key of its own
-    float sum = sT;
-    int len = 1;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t ok_ = (uint32_t)__shfl_down((int)key, d);
-        const bool grow = len == d && lane + d < 64 && ((act >> (lane + d)) & 1ull) && ok_ == key;
-        if (__ballot(grow) == 0ull) break;
-        const float os = __shfl_down(sum, d);
-        const int ol = __shfl_down(len, d);
-        if (grow) {
-            sum += os;
-            len += ol;
-        }
-    }
-    if (jT != 0xffffffffu && !(prv_ok && prv_t == key)) unsafeAtomicAdd(acc + jT, (double)sum);
-}
-
-// Epilogue for 4 consecutive samples: delayed-null replacement where the
-// shifted mask exceeds 1, the observe() pre-noise copy, radiometer noise, store.
-// `pre` holds the data value (FFT output already scaled by 1/N, or the source).
-__device__ __forceinline__ void epilogue4(const KP &k, int r, int64_t n0, int cnt,
-                                          float (&pre)[4], const float (&mask)[4], bool load_data) {
-    const PssPipeline &p = k.p;
-    const uint32_t c = (uint32_t)(p.chan0 + r);
-    float *row = p.data + (int64_t)r * p.ld;
-    PSS_DASSERT(r >= 0 && r < p.nchan && n0 >= 0 && n0 + cnt <= k.N);
-    if (load_data) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) if (i < cnt) pre[i] = row[n0 + i];
-    }
-    if (p.null_mode == PSS_NULL_DELAYED) {
-        const bool any = (mask[0] > 1.0f) | (mask[1] > 1.0f) | (mask[2] > 1.0f) | (mask[3] > 1.0f);
-        if (any) {
-            float x[4];
-            if (p.inj_rep) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) x[i] = (i < cnt) ? p.inj_rep[(int64_t)r * k.N + n0 + i] : 0.f;
-            } else {
-                Rng g(p.seed, p.call_null, P_REP);
-                draw4(g, n0, c, p.null_rep_df, x);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) x[i] *= p.null_rep_scale;
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (i < cnt && mask[i] > 1.0f) pre[i] = x[i];
-        }
-    }
-    if (p.out_kind != PSS_OUT_NONE && p.out_len > 0) {
-        out_windows(p, r, (uint32_t)k.N, (uint32_t)n0, cnt, pre);
-    } else if (p.out_kind == PSS_OUT_F32) {
-        float *o = (float *)p.out + (int64_t)r * k.N;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) if (i < cnt) o[n0 + i] = (pre[i] > p.clip) ? p.clip : pre[i];
-    } else if (p.out_kind == PSS_OUT_I8) {
-        int8_t *o = (int8_t *)p.out + (int64_t)r * k.N;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if (i < cnt) {
-                float v = (pre[i] > p.clip) ? p.clip : pre[i];
-                v = fminf(fmaxf(v, -128.f), 127.f);
-                o[n0 + i] = (int8_t)(int)truncf(v);
-            }
-        }
-    }
-    if (p.noise) {
-        float x[4];
-        if (p.inj_noise) {
-            const float *nr = p.inj_noise + (int64_t)r * k.N;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) x[i] = (i < cnt) ? nr[n0 + i] : 0.f;
-        } else {
-            Rng g(p.seed, p.call_noise, P_NOISE);
-            draw4(g, n0, c, p.noise_df, x);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) pre[i] = fmaf(p.noise_norm, x[i], pre[i]);
-    }
-    if (cnt == 4 && (((uintptr_t)(row + n0)) & 15) == 0) {
-        *reinterpret_cast<float4 *>(row + n0) = make_float4(pre[0], pre[1], pre[2], pre[3]);
-    } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) if (i < cnt) row[n0 + i] = pre[i];
-    }
-}
-
-__device__ __forceinline__ cf apply_ramp_delay(const KP &k, int r, int64_t kb, cf z);
-
-// Scattering-tail transfer function of row r at bin kb (extension, see
-// PssPipeline.tail_a): H = (1 - a) / (1 - a e^{-2 pi i kb/N}); exactly 1 at DC
-// and real (1-a)/(1+a) at Nyquist, Hermitian in kb, so irfft stays real.
-__device__ __forceinline__ cf tail_factor(float a, cf w) {
-    // w = e^{-2 pi i kb / N}; 1/(1 - a w) = conj(d) / |d|^2, d = 1 - a w
-    const float dr = fmaf(-a, w.x, 1.0f), di = -a * w.y;
-    const float s = (1.0f - a) / fmaf(dr, dr, di * di);
-    return make_float2(dr * s, -di * s);
-}
-__device__ __forceinline__ cf bin_phasor(int64_t kb, int64_t N) {
-    const int64_t kk = (2 * kb > N) ? kb - N : kb;
-    return expi_rev(-(float)((double)kk / (double)N));
-}
-
-// exp(-2 pi i k' s / N) for frequency bin k, with the reference's Nyquist
-// rule applied separately to the real (data) and imaginary (mask) parts.
-__device__ __forceinline__ cf apply_ramp(const KP &k, int r, int64_t kb, cf z) {
-    if (k.p.tail_a && !k.p.htab) {
-        const cf h = tail_factor(k.p.tail_a[r], bin_phasor(kb, k.N));
-        const cf t = apply_ramp_delay(k, r, kb, z);
-        if (kb == 0 || 2 * kb == k.N) return make_float2(t.x * h.x, t.y * h.x);   // real parts only
-        return cmul(t, h);
-    }
-    return apply_ramp_delay(k, r, kb, z);
-}
-__device__ __forceinline__ cf apply_ramp_delay(const KP &k, int r, int64_t kb, cf z) {
-    const PssPipeline &p = k.p;
-    const int64_t N = k.N;
-    if (p.htab) {
-        // per-bin transfer function of the rfft bins; Hermitian extension,
-        // DC and Nyquist keep Re H only (irfft drops their imaginary parts)
-        const bool upper = 2 * kb > N;
-        const cf h = reinterpret_cast<const cf *>(p.htab)[upper ? N - kb : kb];
-        if (kb == 0 || 2 * kb == N) return make_float2(z.x * h.x, z.y * h.x);
-        return cmul(z, make_float2(h.x, upper ? -h.y : h.y));
-    }
-    if (2 * kb == N) return make_float2(z.x * p.nyq_re[r], z.y * p.nyq_im[r]);
-    if (kb == 0) return z;
-    const int64_t kk = (2 * kb > N) ? kb - N : kb;
-    const uint64_t ph = (uint64_t)kk * p.ramp[r];
-    return cmul(z, expi_rev(-fix_to_rev(ph)));
-}
-
-// ---------------------------------------------------------------------------
-// path 1: whole row(s) in LDS.  BATCH rows of length L per workgroup.
-// ---------------------------------------------------------------------------
-template <int L, int BATCH, int T, typename FWD, typename INV>
-struct SinglePass;
-
-template <int L, int BATCH, int T, int... F, int... I>
-struct SinglePass<L, BATCH, T, RList<F...>, RList<I...>> {
-    using FF = Fft<L, BATCH, T>;
-    static constexpr int E = FF::E;
-    static constexpr int RF0 = FF::template first<F...>();
-    static constexpr int RFL = FF::template last_of<F...>();
-    static constexpr int RIL = FF::template last_of<I...>();
-    static_assert(RIL == RF0, "inverse plan must be the reversed forward plan");
-
-    __device__ static void body(const KP &k) {
-        __shared__ cf lds[BATCH * Lds<L>::RS];
-        const int tid = threadIdx.x;
-        const int r0 = blockIdx.x * BATCH;
-        const PssPipeline &p = k.p;
-        const bool re_in = p.data_in_fft != 0;
-        // source -> LDS
-        for (int it = tid; it < BATCH * L / 4; it += T) {
-            const int b = it / (L / 4);
-            const int n0 = (it - b * (L / 4)) * 4;
-            float re[4], im[4];
-            if (r0 + b < p.nchan) source4(k, r0 + b, n0, 4, re, im, re_in);
-            else { for (int i = 0; i < 4; ++i) { re[i] = 0.f; im[i] = 0.f; } }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) lds[Lds<L>::at(b, n0 + i)] = make_float2(re[i], im[i]);
-        }
-        __syncthreads();
-        cf v[E];
-        FF::template load<RF0>(v, lds, tid);
-        __syncthreads();
-        FF::template run<false, 1, F...>(v, lds, tid);
-        // ramp on natural-order spectrum (last forward stage mapping)
-#pragma unroll
-        for (int i = 0; i < E; ++i) {
-            int b, pos;
-            FF::template where<RFL>(i, tid, b, pos);
-            const int rr = min(r0 + b, p.nchan - 1);
-            v[i] = apply_ramp(k, rr, pos, v[i]);
-        }
-        FF::template run<true, 1, I...>(v, lds, tid);
-        FF::template store<RIL>(v, lds, tid);
-        __syncthreads();
-        for (int it = tid; it < BATCH * L / 4; it += T) {
-            const int b = it / (L / 4);
-            const int n0 = (it - b * (L / 4)) * 4;
-            if (r0 + b >= p.nchan) continue;
-            float pre[4], msk[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                cf z = lds[Lds<L>::at(b, n0 + i)];
-                pre[i] = z.x * k.invN;
-                msk[i] = z.y * k.invN;
-            }
-            if (k.w1_out) {
-                // (data, mask) for the float64 null refine; the epilogue runs
-                // after it (k_fb_epilogue, as on the other packed paths)
-                cf *w = k.w1_out + (int64_t)(r0 + b) * L + n0;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) w[i] = make_float2(pre[i], msk[i]);
-            } else {
-                epilogue4(k, r0 + b, n0, 4, pre, msk, !re_in);
-            }
-        }
-    }
-};
-
-template <typename SP, int T>
-__global__ __launch_bounds__(T) void k_single(KP k) { SP::body(k); }
 
 // ---------------------------------------------------------------------------
 // path 2: four-step, N = N1 * N2, sample n = N2*n1 + n2, bin k = k1 + N1*k2.
@@ -872,18 +30,19 @@ __global__ __launch_bounds__(T) void k_single(KP k) { SP::body(k); }
 //   B: per (row, BR rows k1): FFT over n2 -> ramp(k) -> inverse FFT over k2
 //   C: per (row, block of B columns n2): * W_N^{-k1 n2}, inverse FFT over k1,
 //      epilogue (null / out / noise), store data[row][N2*n1 + n2]
+// The channels run through it in pairs (path 2b below).  One row at a time
+// only the forward half is left, A (Cols) and the forward transform of B
+// (Rows): the spectrum of the delayed null's mask row (build_mask_table).
 // ---------------------------------------------------------------------------
-template <int N1, int B, int T, typename FWD, typename INV>
+template <int N1, int B, int T, typename FWD>
 struct Cols;
 
-template <int N1, int B, int T, int... F, int... I>
-struct Cols<N1, B, T, RList<F...>, RList<I...>> {
+template <int N1, int B, int T, int... F>
+struct Cols<N1, B, T, RList<F...>> {
     using FF = Fft<N1, B, T>;
     static constexpr int E = FF::E;
     static constexpr int RF0 = FF::template first<F...>();
     static constexpr int RFL = FF::template last_of<F...>();
-    static constexpr int RI0 = FF::template first<I...>();
-    static constexpr int RIL = FF::template last_of<I...>();
 
     __device__ static void passA(const KP &k) {
         __shared__ cf lds[B * Lds<N1>::RS];
@@ -928,70 +87,23 @@ struct Cols<N1, B, T, RList<F...>, RList<I...>> {
             dst[1] = make_float4(a2.x, a2.y, a3.x, a3.y);
         }
     }
-
-    __device__ static void passC(const KP &k) {
-        __shared__ cf lds[B * Lds<N1>::RS];
-        const int tid = threadIdx.x;
-        const int r = blockIdx.y;
-        const int64_t n20 = (int64_t)blockIdx.x * B;
-        const int64_t N2 = k.N2;
-        const float invN = k.invN;
-        const cf *Y = reinterpret_cast<const cf *>(k.p.work) + (int64_t)r * k.N;
-        for (int it = tid; it < N1 * B / 4; it += T) {
-            const int k1 = it / (B / 4);
-            const int b4 = (it - k1 * (B / 4)) * 4;
-            const float4 *src = reinterpret_cast<const float4 *>(Y + (int64_t)k1 * N2 + n20 + b4);
-            float4 lo = src[0], hi = src[1];
-            cf a[4] = {make_float2(lo.x, lo.y), make_float2(lo.z, lo.w),
-                       make_float2(hi.x, hi.y), make_float2(hi.z, hi.w)};
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                int64_t m = (n20 + b4 + i) * (int64_t)k1;
-                float rev = (float)m * invN;
-                if (rev >= 0.5f) rev -= 1.0f;
-                lds[Lds<N1>::at(b4 + i, k1)] = cmul(a[i], expi_rev(rev));
-            }
-        }
-        __syncthreads();
-        cf v[E];
-        FF::template load<RI0>(v, lds, tid);
-        __syncthreads();
-        FF::template run<true, 1, I...>(v, lds, tid);
-        FF::template store<RIL>(v, lds, tid);
-        __syncthreads();
-        const bool re_in = k.p.data_in_fft != 0;
-        for (int it = tid; it < N1 * B / 4; it += T) {
-            const int n1 = it / (B / 4);
-            const int b4 = (it - n1 * (B / 4)) * 4;
-            float pre[4], msk[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                cf z = lds[Lds<N1>::at(b4 + i, n1)];
-                pre[i] = z.x * invN;
-                msk[i] = z.y * invN;
-            }
-            epilogue4(k, r, n1 * N2 + n20 + b4, 4, pre, msk, !re_in);
-        }
-    }
 };
 
 template <typename C, int T>
 __global__ __launch_bounds__(T) void k_colA(KP k) { C::passA(k); }
-template <typename C, int T>
-__global__ __launch_bounds__(T) void k_colC(KP k) { C::passC(k); }
 
-template <int N2, int BR, int T, typename FWD, typename INV, bool FWD_ONLY = false>
+template <int N2, int BR, int T, typename FWD>
 struct Rows;
 
-template <int N2, int BR, int T, int... F, int... I, bool FWD_ONLY>
-struct Rows<N2, BR, T, RList<F...>, RList<I...>, FWD_ONLY> {
+template <int N2, int BR, int T, int... F>
+struct Rows<N2, BR, T, RList<F...>> {
     using FF = Fft<N2, BR, T>;
     static constexpr int E = FF::E;
     static constexpr int RF0 = FF::template first<F...>();
     static constexpr int RFL = FF::template last_of<F...>();
-    static constexpr int RIL = FF::template last_of<I...>();
-    static_assert(RIL == RF0, "inverse plan must be the reversed forward plan");
 
+    // forward transform of BR rows k1, left in natural k2 order per row (the
+    // mask spectrum of pair mode)
     __device__ static void pass(const KP &k) {
         __shared__ cf lds[BR * Lds<N2>::RS];
         const int tid = threadIdx.x;
@@ -1007,30 +119,11 @@ struct Rows<N2, BR, T, RList<F...>, RList<I...>, FWD_ONLY> {
             for (int q = 0; q < RF0; ++q) v[ib * RF0 + q] = Y[(int64_t)b * N2 + jj + q * LR];
         }
         FF::template run<false, 1, F...>(v, lds, tid);
-        if constexpr (FWD_ONLY) {
-            // spectrum in natural k2 order per row k1 (mask spectrum for pair mode)
-#pragma unroll
-            for (int i = 0; i < E; ++i) {
-                int b, k2;
-                FF::template where<RFL>(i, tid, b, k2);
-                Y[(int64_t)b * N2 + k2] = v[i];
-            }
-            return;
-        }
-        const int64_t N1 = k.N1;
 #pragma unroll
         for (int i = 0; i < E; ++i) {
             int b, k2;
             FF::template where<RFL>(i, tid, b, k2);
-            v[i] = apply_ramp(k, r, k10 + b + N1 * (int64_t)k2, v[i]);
-        }
-        __syncthreads();   // LDS reuse by the inverse's first exchange
-        FF::template run<true, 1, I...>(v, lds, tid);
-#pragma unroll
-        for (int ib = 0; ib < E / RF0; ++ib) {
-            const int j = tid + ib * T, b = j / LR, jj = j - b * LR;
-#pragma unroll
-            for (int q = 0; q < RF0; ++q) Y[(int64_t)b * N2 + jj + q * LR] = v[ib * RF0 + q];
+            Y[(int64_t)b * N2 + k2] = v[i];
         }
     }
 };
@@ -1650,7 +743,8 @@ struct PairCols<N1, B, T, RList<F...>, RList<I...>, XRS> {
         const int pra = (p.prof_rows == 1) ? 0 : (int)ca - p.prof_row0, prb = (p.prof_rows == 1) ? 0 : (int)cb - p.prof_row0;
         const Rng g(p.seed, p.call_gen, P_PULSE);
         static_assert(!FAST || kItemsExact, "fast pass A: whole items per thread");
-        if constexpr (FAST && SHARED && kPcol) {
+        if constexpr (FAST && SHARED) {
+            // (host-selected: prof_rows == 1, e.g. C3's GaussProfile)
             // the profile from the per-run sample table (prof_cols): loads
             // issued first, under the Philox draws
             const float dna = hasa ? p.draw_norm : 0.f, dnb = hasb ? p.draw_norm : 0.f;
@@ -1680,13 +774,10 @@ struct PairCols<N1, B, T, RList<F...>, RList<I...>, XRS> {
             const int nint = p.nint;
             const int last = p.prof_rows - 1;
             const int rowa = min(max(pra, 0), last), rowb = min(max(prb, 0), last);
-            // SHARED (host-selected: prof_rows == 1, e.g. C3's GaussProfile):
-            // one table row serves both channels, one lookup and evaluation
-            constexpr bool shared = SHARED;
             const float4 *prof = reinterpret_cast<const float4 *>(p.prof);
             for (int i = tid; i < nint; i += T) {
                 ptab[0][i] = prof[(int64_t)rowa * nint + i];
-                if constexpr (!shared) ptab[1][i] = prof[(int64_t)rowb * nint + i];
+                ptab[1][i] = prof[(int64_t)rowb * nint + i];
             }
             __syncthreads();
             // draw_norm, or 0 for a pair's missing channel (shard / band
@@ -1728,11 +819,8 @@ struct PairCols<N1, B, T, RList<F...>, RList<I...>, XRS> {
                     w.get_full(iv, u);       // fast_source(): nint == knot_m
                     const float4 A = ptab[0][iv];
                     const float pa = fmaf(fmaf(fmaf(A.x, u, A.y), u, A.z), u, A.w);
-                    float pb = pa;
-                    if constexpr (!shared) {
-                        const float4 Bc = ptab[1][iv];
-                        pb = fmaf(fmaf(fmaf(Bc.x, u, Bc.y), u, Bc.z), u, Bc.w);
-                    }
+                    const float4 Bc = ptab[1][iv];
+                    const float pb = fmaf(fmaf(fmaf(Bc.x, u, Bc.y), u, Bc.z), u, Bc.w);
                     lds[LdsC::at(b4 + i, n1)] = make_float2(pa * va[i], pb * vb[i]);
                 }
             }
@@ -2320,279 +1408,6 @@ __global__ __launch_bounds__(T, C::kFoldWaves) void k_pairA_fold(KP k) { C::pass
 template <typename C, int T>
 __global__ __launch_bounds__(T, C::kFoldWavesC) void k_pairC_fold(KP k) { C::passC_fold(k); }
 
-
-static constexpr int64_t kRefineMaxN = 1 << 17;
-static constexpr int kBsParts = 16;
-// refine candidate list capacity (entries of 8 B): 1/8 of the samples + 64 Ki
-// (C4's fold-mode geometry with a null has ~7 % candidates: its boxes are
-// chi2(Nfold ~ 1e4) values, so the band is ~0.3 wide and the boxes' Gibbs
-// ringing crosses it often)
-static inline int64_t refine_cap(int32_t nchan, int64_t N) {
-    const int64_t all = (int64_t)nchan * N;
-    return std::min<int64_t>(all, all / 8 + 65536);
-}
-
-
-// ---------------------------------------------------------------------------
-// entry points of the launch units (one translation unit each, compiled in
-// parallel: psrsigsim_amd/build.py)
-// ---------------------------------------------------------------------------
-int launch_elementwise(const KP &k, hipStream_t st);              // pss_pipeline.hip
-int launch_null_fix(const KP &k, hipStream_t st);                 // pss_fourstep.hip
-int run_fourstep(KP &k, hipStream_t st, const float *mask_row);   // pss_fourstep.hip
-int run_smooth(KP &k, hipStream_t st);                            // pss_smooth.hip (N1 = 6 .. 20)
-int run_smooth_b(KP &k, hipStream_t st);                          // pss_smooth_b.hip (N1 = 24, 30, 40)
-int run_smooth_c(KP &k, hipStream_t st);                          // pss_smooth_c.hip (N1 = 48, 60; 1250 x 2500)
-int run_fourstep_b(KP &k, hipStream_t st, const float *mask_row); // pss_fourstep_b.hip (N != 2^22)
-int run_single(KP &k, hipStream_t st);                            // pss_single.hip
-int run_fallback(KP &k, hipStream_t st);                          // pss_fallback.hip
-int launch_null_refine(KP &k, hipStream_t st);                    // pss_fallback.hip
-int launch_fb_epilogue(KP &k, hipStream_t st);                    // pss_fallback.hip
-int shift_rows_odd(float *rows, int32_t nrows, int64_t n, int64_t ld, const uint64_t *ramp, void *work,
-                   hipStream_t st);                               // pss_fallback.hip
-// the mask-table template's (build_mask_table) non-template kernels, launched
-// through pss_fourstep.hip (each kernel is compiled in one unit only)
-int launch_node_params(uint64_t *ramp, float *nyq, int L, hipStream_t st);
-int launch_mask_table(const float *nodes, int64_t N, uint2 *bits, uint32_t *base, float *coef, uint32_t *counter,
-                      hipStream_t st);
-int launch_mask_words(const uint2 *bits, uint32_t nwords, uint32_t *list, uint32_t *count, hipStream_t st);
-int launch_mask_bits(const KP &k, uint32_t *bm, hipStream_t st);
-
-// ---------------------------------------------------------------------------
-// host dispatch
-// ---------------------------------------------------------------------------
-static inline bool is_pow2(int64_t n) { return n > 0 && (n & (n - 1)) == 0; }
-
-static inline dim3 stream_grid(int64_t items, int rows) {
-    int64_t bx = (items + 255) / 256;
-    if (bx > 4096) bx = 4096;
-    if (bx < 1) bx = 1;
-    return dim3((unsigned)bx, (unsigned)rows, 1);
-}
-
-
-template <int L, int BATCH, int T, typename F, typename I>
-static int launch_single(const KP &k, hipStream_t st) {
-    using SP = SinglePass<L, BATCH, T, F, I>;
-    dim3 grid((k.p.nchan + BATCH - 1) / BATCH);
-    plan_note("single %d", L);
-    tk_begin(TK_SINGLE, st);
-    k_single<SP, T><<<grid, dim3(T), 0, st>>>(k);
-    tk_end(st);
-    LAUNCHCHK();
-    return PSS_OK;
-}
-
-// Column plans: B*N1 = 8192 complex per workgroup, 512 threads, 16 per thread.
-// Inverse plans (..I) mirror the forward ones where registers carry over
-// (single pass, rows); column inverses start from LDS and reuse the forward plan.
-// Row plans: N2 = 8192 (1 row, 512 thr) or N2 <= 4096 (4096/N2 rows, 256 thr).
-using C16 = RList<16>;
-using C32F = RList<16, 2>;
-using C32I = RList<2, 16>;
-using C64F = RList<16, 4>;
-using C64I = RList<4, 16>;
-using C128F = RList<16, 8>;
-using C128I = RList<8, 16>;
-using C256 = RList<16, 16>;
-using C512F = RList<16, 16, 2>;
-using C512I = RList<2, 16, 16>;
-using C1kF = RList<16, 16, 4>;
-using C1kI = RList<4, 16, 16>;
-using C2kF = RList<16, 16, 8>;
-using C2kI = RList<8, 16, 16>;
-using C4k = RList<16, 16, 16>;
-using C8kF = RList<16, 8, 8, 8>;
-using C8kI = RList<8, 8, 8, 16>;
-using C16kF = RList<16, 16, 8, 8>;
-using C16kI = RList<8, 8, 16, 16>;
-
-// ---------------------------------------------------------------------------
-// workspace layout (every region 256-B aligned)
-//   four-step (N = 2^m, 2^14 <= N <= 2^24):
-//     Yd [npairs][N] cf | Mspec [N] cf | node spill [KCH/2][N] cf |
-//     nodes [KCH][N] f32 | table bits [N/64] uint4 | base [N/64] u32 |
-//     coef [N][KREC] f32 (worst case) | misc (counter, node ramps/nyq) |
-//     null bits [nchan][N/32] u32 | mask row [N] f32
-//   single pass (N <= 8192): mask row
-//   direct DFT fallback: W1, W2 [nchan][N] cf | twiddles [N] cf | mask row
-// ---------------------------------------------------------------------------
-static inline int64_t al256(int64_t b) { return (b + 255) & ~255ll; }
-static inline bool fourstep_len(int64_t n) { return is_pow2(n) && n >= 16384 && n <= (1ll << 24); }
-
-// Mixed-radix four-step lengths: even N = N1 * N2 with N2 = 2^m in
-// [1024, 8192] (the largest such power that leaves N1 even) and N1 one of the
-// {2, 3, 4, 5}-smooth column lengths below (e.g. the fold-mode C4 length
-// 30720 = 30 x 1024).  Other even lengths take the direct path.
-static inline bool smooth_col(int64_t n1) {
-    switch (n1) {
-        case 6: case 10: case 12: case 20: case 24: case 30: case 40: case 48: case 60: return true;
-        default: return false;
-    }
-}
-// 5-smooth lengths with few factors of two take an LDS four-step with
-// radix-5 stages both ways: 3 125 000 = 2^3 5^8 (the sample count of the
-// reference's own simulate fixture, tests/test_simulate.py:47-56) as 1250
-// columns (2 x 5^4) x rows of 2500 (4 x 5^4).
-static inline bool smooth5_split(int64_t n, int64_t *N1 = nullptr, int64_t *N2 = nullptr) {
-    if (n != 3125000) return false;
-    if (N1) *N1 = 1250;
-    if (N2) *N2 = 2500;
-    return true;
-}
-static inline bool smooth_split(int64_t n, int64_t *N1 = nullptr, int64_t *N2 = nullptr) {
-    if (smooth5_split(n, N1, N2)) return true;
-    if (n <= 0 || (n & 1) || is_pow2(n) || n > (1ll << 24)) return false;
-    int v2 = __builtin_ctzll((unsigned long long)n);
-    const int m = v2 - 1 < 13 ? v2 - 1 : 13;            // keep N1 even
-    if (m < 10) return false;
-    const int64_t n2 = 1ll << m, n1 = n / n2;
-    if (!smooth_col(n1)) return false;
-    if (N1) *N1 = n1;
-    if (N2) *N2 = n2;
-    return true;
-}
-
-extern int g_flags;   // pss_set_flags (test hook), pss_pipeline.hip
-
-// Bluestein geometry of a fallback length N > 8192 (path 3b): M = M1 x M2,
-// nb channels per convolution batch (the batch buffer is about one W buffer).
-struct BsGeom { int64_t M, M1, M2, nb; };
-static inline bool bs_len(int64_t N) { return N > 8192 && N <= (1ll << 24); }
-static inline BsGeom bs_geom(int32_t nchan, int64_t N) {
-    BsGeom g;
-    g.M = 1;
-    while (g.M < 2 * N - 1) g.M <<= 1;
-    g.M2 = g.M >= (1ll << 25) ? 8192 : 4096;
-    g.M1 = g.M / g.M2;
-    g.nb = ((int64_t)nchan * N + g.M - 1) / g.M;    // (ceil: no near-empty last batch)
-    if (g.nb < 1) g.nb = 1;
-    if (g.nb > nchan) g.nb = nchan;
-    if (g.nb > 65535) g.nb = 65535;
-    return g;
-}
-
-struct WsLayout {
-    int64_t yd, mspec, ynode, nodes, bits, base, coef, misc, mbits, rtab, wlist, row, total;
-    int64_t bs_chirp, bs_bhat, bs_z;   // Bluestein: w [N] | Bhat [M] | Z [nb][M] (cf)
-    int64_t odd_tw;                    // odd N: exp(+2 pi i j / (N - 1)), j < N - 1 (cf)
-    int64_t rf_tw, rf_B, rf_mx;        // float64 null decisions: e^{2 pi i n/N} [N], B [N/2+1] (double2), row max [nchan]
-    int64_t rf_part, rf_list, rf_cnt;  // ... partial spectra [kBsParts][N/2+1] (double2), candidate list, its count
-    int64_t pcol;                      // four-step: the profile at every sample (float4 items, k_prof_cols)
-};
-
-static inline WsLayout ws_layout(int32_t nchan, int64_t N, bool filt = false) {
-    WsLayout w;
-    memset(&w, 0, sizeof(w));
-    int64_t o = 0;
-    if (fourstep_len(N)) {
-        const int64_t npairs = ((int64_t)nchan + 2) / 2;   // pairs of (even, odd) global channels
-        // pair spills: N1 x N2 complex per pair
-        const int64_t ps = N;
-        w.yd = o;    o += al256(npairs * ps * 8);
-        w.mspec = o; o += al256(N * 8);
-        w.ynode = o; o += al256((int64_t)(KCH / 2) * ps * 8);
-        w.nodes = o; o += al256((int64_t)KCH * N * 4);
-        w.bits = o;  o += al256((N / 32) * 8);
-        w.base = o;  o += al256((N / 32) * 4);
-        w.coef = o;  o += al256(N * KREC * 4);
-        w.misc = o;  o += 256;
-        w.mbits = o; o += al256((int64_t)nchan * (N / 8));   // per-channel null bits
-        w.rtab = o;  o += al256(npairs * 2 * 64 * 8);          // row-pass pair ramp factors (RFL <= 64)
-        w.wlist = o; o += al256((N / 32) * 4);                 // null fix-up: table words with nulls
-        w.pcol = o;  o += al256(N * 4);                        // shared-profile pass A: profile per sample
-    } else if (!filt && is_pow2(N) && N >= 64 && N <= 8192) {
-        // single-workgroup lengths: W1 [nchan][N] cf and the float64 null
-        // refine's buffers (a delayed null: run_single)
-        o += al256((int64_t)nchan * N * 8);
-        w.rf_tw = o; o += al256(N * 16);
-        w.rf_B = o;  o += al256((N / 2 + 1) * 16);
-        w.rf_mx = o; o += al256((int64_t)nchan * 4);
-        w.rf_part = o; o += al256((int64_t)kBsParts * (N / 2 + 1) * 16);
-        w.rf_list = o; o += al256(refine_cap(nchan, N) * 8);
-        w.rf_cnt = o;  o += 256;
-    } else if (filt || !(is_pow2(N) && N >= 64 && N <= 8192)) {
-        // fallback: W1, W2, twiddles -- Bluestein needs W1 only (its forward
-        // and inverse DFTs are fused through Z), unless the mixed-radix
-        // four-step shares these bytes or the direct DFT is forced
-        const bool odd = (N & 1) != 0;
-        const bool w1_only = bs_len(N) && !odd && !smooth_split(N) && !(g_flags & PSS_FLAG_DIRECT_DFT);
-        o += al256(w1_only ? (int64_t)nchan * N * 8 : 2 * (int64_t)nchan * N * 8 + N * 8);
-        if (odd) {
-            // odd-length shift_t: twiddles of the (N - 1)-point inverse
-            w.odd_tw = o;
-            o += al256((N - 1) * 8);
-        } else if (bs_len(N)) {
-            const BsGeom g = bs_geom(nchan, N);
-            w.bs_chirp = o; o += al256(N * 8);
-            w.bs_bhat = o;  o += al256(g.M * 8);
-            w.bs_z = o;     o += al256(g.nb * g.M * 8);
-        }
-        if (!odd && N <= kRefineMaxN) {
-            w.rf_tw = o; o += al256(N * 16);
-            w.rf_B = o;  o += al256((N / 2 + 1) * 16);
-            w.rf_mx = o; o += al256((int64_t)nchan * 4);
-            w.rf_part = o; o += al256((int64_t)kBsParts * (N / 2 + 1) * 16);
-            w.rf_list = o; o += al256(refine_cap(nchan, N) * 8);
-            w.rf_cnt = o;  o += 256;
-        }
-        if (smooth_split(N)) {
-            // mixed-radix four-step (inside the same bytes: the direct path
-            // still serves these lengths for a delayed null)
-            const int64_t npairs = ((int64_t)nchan + 2) / 2;
-            w.yd = 0;
-            w.rtab = al256(npairs * N * 8);
-            w.pcol = o; o += al256(N * 4);
-        }
-    }
-    w.row = o;
-    o += al256(N * 4);
-    w.total = o;
-    return w;
-}
-
-// The float64 null decisions of the packed paths (k_null_refine): the
-// direct / Bluestein rows and the single-workgroup kernel's, between the
-// inverse transform (W1 = data + i mask per row) and the epilogue.
-static inline bool refine_null(const KP &k) {
-    return k.p.null_mode == PSS_NULL_DELAYED && (k.N & 1) == 0 && k.N <= kRefineMaxN && !k.p.tail_a &&
-           !k.p.htab && !(g_flags & PSS_FLAG_NULL_F32);
-}
-
-// Fast-path selection (kernels specialised for the north-star configuration;
-// results are bitwise identical to the generic kernels).
-
-static inline bool fast_source(const PssPipeline &p) {
-    if (g_flags & PSS_FLAG_NO_FAST) return false;
-    // (nint == knot_m: the table spans the period, so the fast walk needs no
-    // extrapolation clamp -- pulsar._device_table always builds it so)
-    return p.src == PSS_SRC_SEARCH && !p.gen_amp && p.gen_df == 1.0f && !p.inj_gen && p.null_mode != PSS_NULL_UNDELAYED &&
-           p.nint <= kFastNint && !p.prof_split && (uint32_t)p.nint == p.knot_m;
-}
-// Fold-mode fast passes of the mixed-radix split (PairCols::passA_fold /
-// passC_fold): the fold source with chi2(df != 1) pair draws, and an
-// epilogue of noise only (any df != 1), no injected draws.
-static inline bool fold_source(const PssPipeline &p) {
-    if (g_flags & PSS_FLAG_NO_FAST) return false;
-    return p.src == PSS_SRC_FOLD && !p.gen_amp && !p.inj_gen && p.gen_df != 1.0f && p.nph > 0 &&
-           p.null_mode != PSS_NULL_UNDELAYED;
-}
-static inline bool fold_epilogue(const KP &k) {
-    const PssPipeline &p = k.p;
-    if (g_flags & PSS_FLAG_NO_FAST) return false;
-    if (p.out_kind != PSS_OUT_NONE || p.inj_noise || p.inj_rep) return false;
-    return p.noise && p.noise_df != 1.0f && p.null_mode != PSS_NULL_DELAYED;
-}
-static inline bool fast_epilogue(const KP &k) {
-    const PssPipeline &p = k.p;
-    if (g_flags & PSS_FLAG_NO_FAST) return false;
-    if (p.out_kind != PSS_OUT_NONE || p.inj_noise || p.inj_rep) return false;
-    if (!p.noise || p.noise_df != 1.0f) return false;
-    if (p.null_mode == PSS_NULL_UNDELAYED) return false;
-    if (p.null_mode == PSS_NULL_DELAYED && (!k.mtab || p.null_rep_df != 1.0f)) return false;
-    return (p.ld % 4) == 0 && (((uintptr_t)p.data) & 15) == 0;
-}
-
 // Mask table of a delayed null (see the comment above KCH): mask spectrum,
 // KCH node shifts (KCH/2 pair rows through the row and column engines),
 // Chebyshev coefficients + classification.  Once per run, channel independent.
@@ -2618,8 +1433,8 @@ static inline int build_mask_table(KP &k, hipStream_t st, const float *mask_row,
     km.p.null_mode = PSS_NULL_NONE;
     km.p.data_in_fft = 1;
     km.p.work = mspec;
-    using C1 = Cols<N1, B, T, CF, CI>;
-    using R1 = Rows<N2, 1, TRF, RF, RI, true>;
+    using C1 = Cols<N1, B, T, CF>;
+    using R1 = Rows<N2, 1, TRF, RF>;
     k_colA<C1, T><<<dim3((unsigned)(N2 / B), 1), dim3(T), 0, st>>>(km);
     LAUNCHCHK();
     k_row<R1, TRF><<<dim3((unsigned)N1, 1), dim3(TRF), 0, st>>>(km);
@@ -2701,10 +1516,7 @@ static int launch_pair_passes(KP &k, hipStream_t st, const float *mask_after_a =
 // better after pass A (kernels 23.05-23.12 vs 23.17-23.20 ms) and at 256
 // channels -- a short pass A it slowed by a quarter -- 0.12 ms per step less
 // after pass A (6.52-6.56 vs 6.64-6.68 ms, profiles/r06/ab_mask/)
-#ifndef PSS_MASK_AFTER_A_NCHAN
-#define PSS_MASK_AFTER_A_NCHAN 1024
-#endif
-static constexpr int kMaskAfterANchan = PSS_MASK_AFTER_A_NCHAN;
+static constexpr int kMaskAfterANchan = 1024;
 
 // BC/TC: column-block width and threads of the FAST pass C (the spill layout
 // does not depend on the block width, so pass C may use wider blocks than pass
@@ -2790,14 +1602,13 @@ static int launch_pair_passes(KP &k, hipStream_t st, const float *mask_after_a) 
     } else if constexpr (PC::kItemsExact) {
         if (fast_source(k.p)) {
             if (k.p.prof_rows == 1) {
-                if constexpr (kPcol) {
-                    float4 *pcol = reinterpret_cast<float4 *>(reinterpret_cast<char *>(k.p.work) +
-                                                              ws_layout(k.p.nchan, k.N).pcol);
-                    const int64_t ne = k.N / 4;
-                    k_prof_cols<PC><<<dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st>>>(k, pcol);
-                    LAUNCHCHK();
-                    k.pcol = pcol;
-                }
+                // the shared profile at every sample, once per run (PairCols::prof_cols)
+                float4 *pcol = reinterpret_cast<float4 *>(reinterpret_cast<char *>(k.p.work) +
+                                                          ws_layout(k.p.nchan, k.N).pcol);
+                const int64_t ne = k.N / 4;
+                k_prof_cols<PC><<<dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st>>>(k, pcol);
+                LAUNCHCHK();
+                k.pcol = pcol;
                 k_pairA_fast<PC, T, true><<<gc, dim3(T), 0, st>>>(k);
             } else {
                 k_pairA_fast<PC, T, false><<<gc, dim3(T), 0, st>>>(k);
@@ -2868,7 +1679,7 @@ static int launch_pair_passes(KP &k, hipStream_t st, const float *mask_after_a) 
                 k_pairC_fast32<PairCols<N1, 16, 512, CF, CI, -1>, 512>
                     <<<dim3((unsigned)(N2 / 16), (unsigned)k.npairs), dim3(512), 0, st>>>(k);
                 plan_note(" C:fast32");
-            } else if constexpr (kPassCCols16 && N1 == 1024 && N2 % 16 == 0) {
+            } else if constexpr (N1 == 1024 && N2 % 16 == 0) {
                 k_pairC_fast32<PairCols<N1, 16, 512, CF, CI, -1>, 512, 4>
                     <<<dim3((unsigned)(N2 / 16), (unsigned)k.npairs), dim3(512), 0, st>>>(k);
                 plan_note(" C:fast C:cols16x2");

@@ -1,6 +1,6 @@
 // pss_fourstep_b.hip -- the power-of-two four-step lengths other than C3's 2^22
 // (2^14 .. 2^21, 2^23, 2^24), compiled in parallel with pss_fourstep.hip.
-#include "pss_engine.hpp"
+#include "pss_fourstep.hpp"
 
 using namespace pss;
 

@@ -1,24 +1,11 @@
-// pss_pipeline.hip -- fused filterbank synthesis engine for MI355X (gfx950).
-//
-// One PssPipeline run = source -> [FFT delay ramp] -> [null] -> [noise] -> data.
-// See include/pss_hip.h for the ABI and DESIGN.md for the kernel/roofline
-// discussion.  Paths:
-//   * no delay stage           : k_elementwise          (1 HBM pass)
-//   * N = 2^m, 64 <= N <= 8192 : k_single<L>            (1 HBM pass, FFT in LDS)
-//   * N = 2^m, N >= 16384      : k_colA -> k_row -> k_colC  (four-step, 2 spills)
-//   * 2^m x {6..60} (smooth)   : mixed-radix four-step
-//   * other even N <= 8192     : direct DFT              (O(N^2) in LDS tiles)
-//   * other even N >  8192     : Bluestein chirp-z through a 2^m four-step
-#include <hip/hip_runtime.h>
+// pss_pipeline.hip -- fused filterbank synthesis engine for MI355X (gfx950):
+// the C-ABI's entry points, validation and the dispatch of a run to its path
+// (the paths are listed in pss_plan.hpp), the path without a delay stage and
+// the small utility kernels.
 #include <stdarg.h>
-#include <stdint.h>
 #include <stdio.h>
-#include <string.h>
-#include <math.h>
-#include <type_traits>
 
-
-#include "pss_engine.hpp"
+#include "pss_stages.hpp"
 
 using namespace pss;
 
@@ -79,21 +66,6 @@ void plan_note(const char *fmt, ...) {
     const int w = vsnprintf(g_plan + g_plan_len, sizeof(g_plan) - g_plan_len, fmt, ap);
     va_end(ap);
     if (w > 0) g_plan_len = std::min(g_plan_len + (size_t)w, sizeof(g_plan) - 1);
-}
-
-SideStreams *side_streams() {
-    static SideStreams g[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-    SideStreams &x = g[dev];
-    if (!x.ok) {
-        for (int i = 0; i < 2; ++i)
-            if (hipStreamCreateWithFlags(&x.s[i], hipStreamNonBlocking) != hipSuccess) return nullptr;
-        for (int i = 0; i < 40; ++i)
-            if (hipEventCreateWithFlags(&x.ev[i], hipEventDisableTiming) != hipSuccess) return nullptr;
-        x.ok = true;
-    }
-    return &x;
 }
 
 // Delayed null: the (pre-shift) box mask is the same for every channel, so it

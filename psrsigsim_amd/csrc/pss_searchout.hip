@@ -9,7 +9,7 @@
 //                             codes; a 64-sample x 64-output-byte tile per
 //                             workgroup pass, transposed through LDS as packed
 //                             dwords.
-#include "pss_engine.hpp"
+#include "pss_common.hpp"
 
 using namespace pss;
 
@@ -205,8 +205,7 @@ static int launch_quantize(const float *data, int64_t ld, int32_t nchan, int64_t
     dim3 g = stream_grid(ntiles * 256, (int)((rowbytes + QG * 4 - 1) / (QG * 4)));
     // 16-B loads and whole-dword stores need the alignment; anything else
     // takes the element-wise path (same codes)
-    const bool fast = ((uintptr_t)data % 16 == 0) && ld % 4 == 0 && nsblk % 4 == 0 && rowbytes % 4 == 0 &&
-                      ((uintptr_t)out % 4 == 0);
+    const bool fast = on_grid16(data, ld) && nsblk % 4 == 0 && rowbytes % 4 == 0 && ((uintptr_t)out % 4 == 0);
     if (fast)
         k_quantize<NBITS, true><<<g, dim3(256), 0, st>>>(data, ld, nchan, nsblk, nrows, scl, offs, out);
     else
@@ -226,7 +225,7 @@ int pss_chan_stats(const float *data, int32_t nchan, int64_t ld, int64_t nsblk, 
     if (nrows > ld / nsblk) return fail(PSS_EINVAL, "chan_stats: ld %lld < %lld rows of %lld samples", (long long)ld,
                                         (long long)nrows, (long long)nsblk);
     dim3 g = stream_grid((nrows + 3) / 4 * 256, nchan);
-    const bool vec = ((uintptr_t)data % 16 == 0) && ld % 4 == 0 && nsblk % 4 == 0;
+    const bool vec = on_grid16(data, ld) && nsblk % 4 == 0;
     if (vec)
         k_chan_stats<true><<<g, dim3(256), 0, (hipStream_t)stream>>>(data, ld, nchan, nsblk, nrows, mn, mx, sum, sumsq);
     else

@@ -1,7 +1,7 @@
 // pss_smooth.hip -- the mixed-radix four-step (2^m x {6..60}, 1250 x 2500):
 // the dispatch and N1 = 6 .. 20 (the other column lengths: pss_smooth_b/c.hip,
 // compiled in parallel).
-#include "pss_engine.hpp"
+#include "pss_fourstep.hpp"
 
 using namespace pss;
 

@@ -1,5 +1,5 @@
 // pss_smooth_b.hip -- mixed-radix four-step, N1 = 24, 30 (fold-mode C4's 30 x 1024), 40.
-#include "pss_engine.hpp"
+#include "pss_fourstep.hpp"
 
 using namespace pss;
 

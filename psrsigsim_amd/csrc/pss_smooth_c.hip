@@ -1,5 +1,5 @@
 // pss_smooth_c.hip -- mixed-radix four-step, N1 = 48, 60 and 3 125 000 = 1250 x 2500.
-#include "pss_engine.hpp"
+#include "pss_fourstep.hpp"
 
 using namespace pss;
 

@@ -84,6 +84,35 @@ def test_workspace_sizes():
         assert L.pss_workspace_bytes(2, n) == a(5 * n * 8) + f64(n, 2) + a(n * 8) + 2 * a(32768 * 8) + a(n * 4)
     finally:
         L.pss_set_flags(old)
+    # mixed-radix four-step (30 x 1024) inside the fallback's bytes: W1, W2,
+    # twiddles | Bluestein (M = 65536, nb = ceil(4 x 30720 / M) = 2) | float64
+    # null refine | the shared-profile pass A's sample table | mask row
+    n, M = 30720, 65536
+    assert L.pss_workspace_bytes(4, n) == (a(9 * n * 8) + a(n * 8) + a(M * 8) + a(2 * M * 8) + f64(n, 4)
+                                           + a(n * 4) + a(n * 4))
+    # 3 125 000 = 1250 x 2500: the same without the refine (N > 2^17); M = 2^23, nb = 1
+    n, M = 3125000, 1 << 23
+    assert L.pss_workspace_bytes(2, n) == a(5 * n * 8) + a(n * 8) + 2 * a(M * 8) + a(n * 4) + a(n * 4)
+    # an odd length (pss_shift_rows): W1, W2, twiddles | the (N - 1)-point inverse's twiddles | row
+    n = 1001
+    assert L.pss_workspace_bytes(3, n) == a(7 * n * 8) + a((n - 1) * 8) + a(n * 4)
+    # the filter variant keeps a single-workgroup length on the fallback's
+    # layout and a four-step length on the four-step's
+    assert L.pss_filter_workspace_bytes(2, 4096) == a(5 * 4096 * 8) + f64(4096, 2) + 4096 * 4
+    assert L.pss_filter_workspace_bytes(4, 1 << 20) == L.pss_workspace_bytes(4, 1 << 20)
+
+
+def test_every_included_header_is_hashed():
+    """Every project header a unit of csrc/ includes is one of build.DEPS, so
+    an edit to it rebuilds the library."""
+    from psrsigsim_amd import build
+    csrc = os.path.join(ROOT, "psrsigsim_amd", "csrc")
+    deps = {os.path.basename(d) for d in build.DEPS}
+    included = set()
+    for f in os.listdir(csrc):
+        if f.endswith((".hip", ".hpp", ".cpp")):
+            included.update(re.findall(r'#include\s+"(pss_\w+\.hpp)"', open(os.path.join(csrc, f)).read()))
+    assert included and included <= deps, included - deps
 
 
 def test_struct_layout_matches_header(tmp_path):

@@ -93,6 +93,13 @@ def _case(name):
         sp = np.ptp(tab[:ND], axis=0)
         assert sp[2] == 0 and sp[4] == SPREAD and sp[5] > SPREAD and (sp > SPREAD).sum() >= 4
         return int_data(7, 6000, 9), tab, 3500
+    if name == "runs12":
+        # 4 time tiles x 3 trial groups = 12 workgroups: more than the 8 XCDs and
+        # no multiple of 8, so the XCD run map's runs differ in length (the other
+        # cases launch 1 .. 6 workgroups, or 16)
+        tab = physical_table(17)
+        md = int(tab.max())
+        return int_data(64, 3 * TB + 5 + md, 12), tab, md
     raise KeyError(name)
 
 
@@ -142,7 +149,7 @@ def run_kernel(hip_lib, data, table, max_delay, ld=None, out_ld=None, in_off=0, 
     return rows[:, :T].copy()
 
 
-KERNEL_CASES = ["copy", "odd", "physical", "growing", "channels", "ragged", "wide"]
+KERNEL_CASES = ["copy", "odd", "physical", "growing", "channels", "ragged", "wide", "runs12"]
 
 
 @pytest.mark.parametrize("name", KERNEL_CASES)
