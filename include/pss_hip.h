@@ -441,6 +441,59 @@ int pss_boxcar_search(const float *plane, int32_t ndm, int64_t T, int64_t ld, co
                       const float *rstd, int32_t nw, int32_t cell, float *snr, int32_t *code,
                       int64_t out_ld, void *stream);
 
+/*
+ * Periodicity search of a DM-time plane (extension, no reference
+ * counterpart): the incoherent harmonic sum of the power spectrum of every
+ * trial.  spec[ndm][ld] is a complex spectrum (interleaved float32 re / im, ld
+ * in complex elements, nbin usable bins per row -- the rfft of a trial without
+ * its Nyquist bin), scale[ndm] a device array; per trial and per cell of `cell`
+ * consecutive bins, nq = ceil(nbin / cell) cells, the best sum of 2^l
+ * harmonics, l < nl, is kept.  All arithmetic is IEEE float32, every line one
+ * rounded operation, no fused multiply-add:
+ *   P[k]       = ((re_k * re_k) + (im_k * im_k)) * scale[j]             k < nbin
+ *   idx(k,m,h) = floor((k * m + h/2) / h)    (integers, h/2 = 0 at h = 1: the
+ *                                             bin nearest to k m / h, <= k)
+ *   H_0[k]     = P[k]
+ *   H_l[k]     = H_{l-1}[k], then for m = 1, 3, 5 .. h - 1 (h = 2^l) in that
+ *                order:  H += P[idx(k,m,h)]
+ *   z_l[k]     = (H_l[k] - h) * a_l,  a_l = 2^-ceil(l/2) * (l odd ? 0x3FB504F3 : 1)
+ *   valid      : l < nl, k < nbin, idx(k,1,h) >= kmin
+ *   cell q     : the lexicographic maximum of (z, -l, -k) over the valid (l, k)
+ *                with q * cell <= k < min((q + 1) * cell, nbin): the largest z;
+ *                ties go to the lower level, then to the lower bin; a NaN z
+ *                never wins
+ *   snr[j * out_ld + q]  = that z, -inf if no candidate was greater than -inf
+ *   code[j * out_ld + q] = (l << 16) | (k - q * cell), 0 with a -inf result
+ * k is the bin of the highest of the h harmonics and the fundamental sits at
+ * k / h bins (summing from the top): every term of a sum lies at or below k,
+ * and at or above the fundamental's bin, so no read leaves [kmin, nbin) of the
+ * row.  The even m of level l are the terms of level l - 1 (idx(k, 2m', 2h') =
+ * idx(k, m', h')), which makes the recurrence the full sum over m = 1 .. h.
+ * a_l is 2^(-l/2) as in pss_boxcar_search; with scale = 1 / (sigma^2 n) for a
+ * series of n samples of variance sigma^2 the powers of white noise are exp(1)
+ * variables and z is the sum in units of its own standard deviation.  The
+ * fixed order of the adds makes the bits independent of the tile, the
+ * alignment of spec / ld / out_ld and the run.  Nothing is written outside
+ * snr / code [j * out_ld + 0 .. nq).  A workgroup owns 2048 bins k of one
+ * trial and gathers the terms; no atomics.
+ * work is NULL or a device buffer of ndm * nbin floats.  With it a first pass
+ * writes the powers P[j][k], kmin <= k < nbin, there and the sums gather
+ * dwords from rows half as long as the spectrum's, each power computed once
+ * rather than once per term -- faster from nl = 4 on, twice as fast at nl = 5,
+ * and slower below, down to nl = 1, where every bin is read once anyway
+ * (measured: DESIGN.md section 9).
+ * Without it the sums gather from the spectrum itself.  The operations and
+ * their order are the same either way, and so are the bits; work holds
+ * nothing of use afterwards and must not overlap the other buffers.
+ * PSS_EINVAL (nothing launched) on a NULL pointer other than work, ndm < 1,
+ * nbin < 1, nbin > 2^27 (k * 16 + 8 in 31 bits), ld < nbin, nl outside [1, 5],
+ * kmin < 1, cell not a power of two in [16, 2048], out_ld < nq, and when
+ * ceil(nbin / 2048) * ndm exceeds 2^31 - 1 (the launch grid).
+ */
+int pss_harmonic_search(const float *spec, int32_t ndm, int64_t nbin, int64_t ld, const float *scale,
+                        int32_t nl, int64_t kmin, int32_t cell, float *snr, int32_t *code, int64_t out_ld,
+                        float *work, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
