@@ -239,6 +239,27 @@ double pss_timing_span_ms(void);
 /* Workspace bytes the fused run needs for `nchan` rows of length `nsamp`. */
 int64_t pss_workspace_bytes(int32_t nchan, int64_t nsamp);
 
+/* The FFT plan a delay-stage run of `nsamp` samples per row takes (host only,
+ * no GPU touched): returns its kind and writes the geometry to n1 x n2
+ * (either may be NULL) --
+ *   SINGLE      one workgroup per row(s), 2^m in [64, 8192]: 1 x nsamp
+ *   FOURSTEP    power-of-two four-step: columns x rows (N1 x N2)
+ *   SMOOTH      mixed-radix four-step: N1 x N2
+ *   DIRECT      O(N^2) direct DFT: 0 x 0 (no split)
+ *   BLUESTEIN   chirp-z through an M1 x M2 power-of-two four-step
+ *   UNSUPPORTED odd or non-positive nsamp, other lengths above 2^24
+ * `variant`: 0 a delay only, 1 with a delayed null (null_mode
+ * PSS_NULL_DELAYED), 2 with a transfer function or the scattering tail (htab
+ * / tail_a) and no delayed null.  Honours PSS_FLAG_DIRECT_DFT.  These are
+ * the functions pss_run's launchers take their split from. */
+#define PSS_PLAN_UNSUPPORTED 0
+#define PSS_PLAN_SINGLE 1
+#define PSS_PLAN_FOURSTEP 2
+#define PSS_PLAN_SMOOTH 3
+#define PSS_PLAN_DIRECT 4
+#define PSS_PLAN_BLUESTEIN 5
+int pss_plan_geometry(int64_t nsamp, int32_t variant, int64_t *n1, int64_t *n2);
+
 /* The fused run (see PssPipeline). */
 int pss_run(const PssPipeline *p, void *stream);
 

@@ -57,6 +57,7 @@ EXPORTS = {
     "pss_last_error": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t]),
     "pss_plan_collect": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t]),
     "pss_workspace_bytes": (c_i64, [c_i32, c_i64]),
+    "pss_plan_geometry": (ctypes.c_int, [c_i64, c_i32, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
     "pss_timing_enable": (None, [ctypes.c_int]),
     "pss_timing_span_ms": (ctypes.c_double, []),
     "pss_timing_collect": (ctypes.c_int, [ctypes.POINTER(c_i32), ctypes.POINTER(ctypes.c_double),
@@ -157,6 +158,18 @@ def plan_collect():
     buf = ctypes.create_string_buffer(16384)
     load().pss_plan_collect(buf, 16384)
     return [l for l in buf.value.decode(errors="replace").split("\n") if l]
+
+
+PLAN_KINDS = ("unsupported", "single", "fourstep", "smooth", "direct", "bluestein")
+
+
+def plan_geometry(nsamp, variant=0):
+    """(kind, N1, N2) of the FFT plan a delay-stage run of ``nsamp`` samples
+    takes (pss_plan_geometry; host only).  ``variant``: 0 a delay only, 1 with
+    a delayed null, 2 with a transfer function or the scattering tail."""
+    n1, n2 = c_i64(0), c_i64(0)
+    kind = load().pss_plan_geometry(int(nsamp), int(variant), ctypes.byref(n1), ctypes.byref(n2))
+    return PLAN_KINDS[kind], n1.value, n2.value
 
 
 def last_error():

@@ -337,13 +337,12 @@ int launch_null_fix(const KP &k, hipStream_t st) {
 }
 
 int run_fourstep(KP &k, hipStream_t st, const float *mask_row) {
-    const int64_t N = k.N;
+    if (!fourstep_split(k.N, plan_variant(k.p) == 0, &k.N1, &k.N2))
+        return fail(PSS_EUNSUPPORTED, "four-step: N=%lld", (long long)k.N);
     plan_note("fourstep");
-    if (N == (1 << 22)) {
+    if (k.N1 == 1024 && k.N2 == 4096) {
         // C3: 1024 x 4096 (two 4096-point rows of a pair in 66 KB: two row
         // workgroups per CU; 16-column pass-C blocks, 64-B output segments)
-        k.N2 = 4096;
-        k.N1 = 1024;
         return launch_pair<1024, 8, 512, C1kF, C1kF, 4096, 512, C4k, C4k, 256, kBC, kTC>(k, st, mask_row);
     }
     return run_fourstep_b(k, st, mask_row);

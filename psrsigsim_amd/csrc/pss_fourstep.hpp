@@ -1326,7 +1326,19 @@ struct PairCols<N1, B, T, RList<F...>, RList<I...>, XRS> {
         const uint32_t rbytes = (uint32_t)(k.N * 4);
         const Buf oa(p.data + (int64_t)max(ra, 0) * p.ld, rbytes), ob(p.data + (int64_t)min(rb, p.nchan - 1) * p.ld, rbytes);
         const int64_t n20 = (int64_t)cbx * B;
-        inv_block(k, k.Yd + (int64_t)pr * pstride(k), n20, lds, tid);
+        if constexpr (kRegCols) {
+            // register columns (mixed radix, N1 = 12 .. 60): the inverse of
+            // passC -- reg_unspill's per-element twiddles and RegDft, not
+            // inv_block's LDS transform with composed twiddles, whose
+            // roundings differ in the last bit
+            cf x[N1];
+            reg_unspill(k, x, pr, n20 + tid);
+#pragma unroll
+            for (int n1 = 0; n1 < N1; ++n1) lds[LdsC::at(tid, n1)] = x[n1];
+            __syncthreads();
+        } else {
+            inv_block(k, k.Yd + (int64_t)pr * pstride(k), n20, lds, tid);
+        }
         float acc[ITEMS][2][4];
 #pragma unroll
         for (int t = 0; t < ITEMS; ++t) {

@@ -388,6 +388,15 @@ int64_t pss_workspace_bytes(int32_t nchan, int64_t nsamp) {
     return ws_layout(nchan, nsamp).total;
 }
 
+int pss_plan_geometry(int64_t nsamp, int32_t variant, int64_t *n1, int64_t *n2) {
+    if (variant < 0 || variant > 2) {
+        if (n1) *n1 = 0;
+        if (n2) *n2 = 0;
+        return PSS_PLAN_UNSUPPORTED;
+    }
+    return plan_geometry(nsamp, variant, n1, n2);
+}
+
 static int run_paths(const PssPipeline *p, hipStream_t st);
 
 int pss_run(const PssPipeline *p, void *stream) {
@@ -430,10 +439,12 @@ static int run_paths(const PssPipeline *p, hipStream_t st) {
             row = const_cast<float *>(p->inj_box);
         }
     }
-    if (is_pow2(N) && N >= 64 && N <= 8192) return run_single(k, st);
-    if (is_pow2(N) && N >= 16384 && N <= (1ll << 24)) return run_fourstep(k, st, row);
-    if (smooth_split(N) && p->null_mode != PSS_NULL_DELAYED) return run_smooth(k, st);
-    return run_fallback(k, st);
+    switch (plan_geometry(N, plan_variant(*p))) {
+        case PSS_PLAN_SINGLE: return run_single(k, st);
+        case PSS_PLAN_FOURSTEP: return run_fourstep(k, st, row);
+        case PSS_PLAN_SMOOTH: return run_smooth(k, st);
+        default: return run_fallback(k, st);
+    }
 }
 
 

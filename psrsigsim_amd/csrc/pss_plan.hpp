@@ -83,6 +83,25 @@ static constexpr int kFastNint = 376;
 // length classification
 // ---------------------------------------------------------------------------
 static inline bool fourstep_len(int64_t n) { return is_pow2(n) && n >= 16384 && n <= (1ll << 24); }
+// The power-of-two four-step's N = N1 x N2 (columns x rows; run_fourstep and
+// run_fourstep_b launch the kernels of the split this returns):
+//   2^14 .. 2^16 : 16 columns, rows of N / 16
+//   2^17 .. 2^22 : rows of 4096 (two rows of a pair in 66 KB of LDS), N / 4096 columns
+//   2^23         : 1024 x 8192
+//   2^24         : 1024 x 16384 for a plain delay (C5: one-row-at-a-time row
+//                  pass); with a delayed null (the mask table's row engine
+//                  holds a pair of rows), a transfer function or the tail
+//                  (`plain` false): 2048 x 8192
+static inline bool fourstep_split(int64_t n, bool plain, int64_t *N1 = nullptr, int64_t *N2 = nullptr) {
+    if (!fourstep_len(n)) return false;
+    int64_t n2 = 4096;
+    if (n == (1ll << 24)) n2 = plain ? 16384 : 8192;
+    else if (n == (1ll << 23)) n2 = 8192;
+    else if (n < (1ll << 17)) n2 = n / 16;
+    if (N1) *N1 = n / n2;
+    if (N2) *N2 = n2;
+    return true;
+}
 
 // Mixed-radix four-step lengths: even N = N1 * N2 with N2 = 2^m in
 // [1024, 8192] (the largest such power that leaves N1 even) and N1 one of the
@@ -134,6 +153,36 @@ static inline BsGeom bs_geom(int32_t nchan, int64_t N) {
     if (g.nb > nchan) g.nb = nchan;
     if (g.nb > 65535) g.nb = 65535;
     return g;
+}
+
+// The plan of a delay-stage run (pss_plan_geometry, include/pss_hip.h), in
+// the order run_paths tries the paths -- run_paths dispatches on the kind
+// this returns, and the launchers take N1 x N2 from the same split functions.
+static inline int plan_variant(const PssPipeline &p) {
+    return p.null_mode == PSS_NULL_DELAYED ? 1 : (p.htab || p.tail_a) ? 2 : 0;
+}
+static inline int plan_geometry(int64_t N, int variant, int64_t *N1 = nullptr, int64_t *N2 = nullptr) {
+    int64_t n1 = 0, n2 = 0;
+    int kind = PSS_PLAN_DIRECT;
+    if (N <= 0 || (N & 1) || (N > (1ll << 24) && !is_pow2(N))) {
+        kind = PSS_PLAN_UNSUPPORTED;                 // (validate() rejects these)
+    } else if (is_pow2(N) && N >= 64 && N <= 8192) {
+        kind = PSS_PLAN_SINGLE;
+        n1 = 1;
+        n2 = N;
+    } else if (fourstep_split(N, variant == 0, &n1, &n2)) {
+        kind = PSS_PLAN_FOURSTEP;
+    } else if (variant != 1 && smooth_split(N, &n1, &n2)) {
+        kind = PSS_PLAN_SMOOTH;                      // (a delayed null off 2^m: the packed paths)
+    } else if (bs_len(N) && !(g_flags & PSS_FLAG_DIRECT_DFT)) {
+        const BsGeom g = bs_geom(1, N);
+        kind = PSS_PLAN_BLUESTEIN;
+        n1 = g.M1;
+        n2 = g.M2;
+    }
+    if (N1) *N1 = n1;
+    if (N2) *N2 = n2;
+    return kind;
 }
 
 static constexpr int64_t kRefineMaxN = 1 << 17;

@@ -51,16 +51,21 @@ def test_baseband_golden_exact(tag, hip_lib):
         ISM().disperse(sig, dm)
 
 
-@pytest.mark.parametrize("N", [4096, 51200, 1 << 16, 100002, 20480, 1 << 22, 1 << 23, 1 << 24, 196608, 3125000])
+@pytest.mark.parametrize("N", [4096, 51200, 1 << 16, 100002, 20480, 1 << 22, 1 << 23, 1 << 24, 196608, 3125000,
+                               6144, 1 << 14])
 def test_filter_rows_vs_numpy(N, hip_lib):
     """The transfer-function run against numpy irfft(rfft(x) H) in float64:
     single pass (4096), the pair four-step with H in the row pass (2^16,
     2^22; 8192-point rows at 2^23 = 1024 x 8192 and 2^24 = 2048 x 8192; the
     mixed-radix 10 x 2048 split at 20480 and 24 x 8192 at 196608; the radix-5
-    1250 x 2500 split at 3 125 000), Bluestein (51200, 100002).  (ADVICE r04:
-    every row-pass instantiation the htab runs can take.)"""
+    1250 x 2500 split at 3 125 000; 1024-point rows at 6144 = 6 x 1024 and
+    2^14 = 16 x 1024), Bluestein (51200, 100002).  (every
+    row-pass instantiation the htab runs can take.)  The launch plan must
+    show the geometry of tests/fft_geometries.py and, on the four-step
+    splits, the transfer-function row pass."""
     import torch
-    from psrsigsim_amd import _engine
+    from psrsigsim_amd import _engine, _lib
+    from tests import fft_geometries, replay
     rng = np.random.default_rng(N)
     x = rng.standard_normal((3, N)).astype(np.float32)
     H = np.exp(1j * 2 * np.pi * rng.random(N // 2 + 1) * 50.0)
@@ -70,8 +75,12 @@ def test_filter_rows_vs_numpy(N, hip_lib):
             self.data = t
 
     s = _S(torch.from_numpy(x).cuda())
+    _lib.plan_collect()
     _engine.filter_rows(s, H)
     got = s.data.cpu().numpy()
+    g = fft_geometries.of_length(N, 2)
+    replay.assert_plan(_lib.plan_collect(), 3, N,
+                       g.tokens + (("R:pair_row_htab",) if g.kind in ("fourstep", "smooth") else ()))
     ref = np.fft.irfft(np.fft.rfft(x.astype(np.float64), axis=1) * H.astype(np.complex64), axis=1)
     assert _err(got, ref) <= TOL
 

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 from oracle import pss_cpu as O
-from tests import replay
+from tests import fft_geometries, replay
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
@@ -21,28 +21,16 @@ def test_golden_replay(name, fused, hip_lib):
     assert not bad, errs
 
 
-SIZES = [64, 128, 256, 512, 1024, 2048, 4096, 8192, 16384, 32768, 65536, 1 << 17, 1 << 18,
-         1 << 20, 1 << 23, 244, 1000, 30720,
-         # mixed-radix four-step: N1 x N2 = 6 x 2048, 10 x 4096, 30 x 2048, 30 x 4096, 24 x 8192
-         12288, 40960, 61440, 122880, 196608,
-         # Bluestein (chirp-z) fallback: M1 x M2 = 8 x 4096 (2 x 5003), 64 x 4096,
-         # 1024 x 4096 (2^20 - 2), 4096 x 8192 (2^24 - 2); and the reference
-         # simulate fixture's 3 125 000 = 2^3 5^8 (radix-5 four-step 1250 x 2500)
-         10006, 100002, (1 << 20) - 2, 3125000, (1 << 24) - 2]
+# (the lengths live with the geometry table; the table's other delay-only
+# lengths run in tests/test_gpu_fft_geometries.py)
+SIZES = list(fft_geometries.PARITY_SWEEP)
 
 
 @pytest.mark.parametrize("N", SIZES)
 def test_shift_t_rows_vs_oracle(N, hip_lib):
-    from psrsigsim_amd.utils import shift_t
-    rng = np.random.default_rng(N)
-    R = 3 if N <= (1 << 18) else (2 if N <= (1 << 22) else 1)
-    x = rng.random((R, N)).astype(np.float32)
-    shifts = np.array([0.37, -1234.5678, 3.0 * N + 17.25][:R])
-    got = shift_t(x, shifts, dt=1.0)
-    for r in range(R):
-        ref = O.shift_t(x[r].astype(np.float64), float(shifts[r]), dt=1.0)
-        err = np.max(np.abs(got[r] - ref)) / np.max(np.abs(ref))
-        assert err < TOL, (N, r, err)
+    """utils.shift_t against the float64 oracle, and the kernels of N's
+    geometry in the launch plan (fft_geometries.check_shift_rows)."""
+    fft_geometries.check_shift_rows(N, TOL)
 
 
 @pytest.mark.parametrize("N", [10006, 100002])

@@ -120,11 +120,15 @@ def test_fast_path_bitwise_equals_generic(nchan, log2n, null, dm, hip_lib):
 F0_B1855 = 186.4940812499314404
 
 
+# the split each (tobs, bins) geometry below must take (asserted in the launch plan)
+FOLD_SPLITS = {(1800.0, 1024): "30x1024", (600.0, 1024): "10x1024", (720.0, 2048): "6x4096"}
+
+
 @pytest.mark.parametrize("nchan,shard,tobs,samprate_bins", [
     (4, None, 1800.0, 1024),          # C4's geometry: 30 x 1024 (register columns, 30-point DFT)
     (5, (1, 4), 1800.0, 1024),        # odd shard start: pair (0, 1) misses channel 0
     (3, None, 600.0, 1024),           # 10 subints: 10 x 1024
-    (2, None, 720.0, 2048),           # 12 subints of 2048 bins: 24 x 1024
+    (2, None, 720.0, 2048),           # 12 subints of 2048 bins: 24576 samples = 6 x 4096
 ])
 def test_fold_fast_bitwise_equals_generic(nchan, shard, tobs, samprate_bins, hip_lib):
     """Fold mode on the mixed-radix split: the fold fast kernels
@@ -132,8 +136,13 @@ def test_fold_fast_bitwise_equals_generic(nchan, shard, tobs, samprate_bins, hip
     lanes of a column pair, one DPP swap) against the generic kernels
     (source4 / epilogue4 draws through LDS), bit for bit; the generic path is
     itself checked against the oracle with injected draws
-    (test_gpu_parity.py::test_c4_fold_mixed_radix_vs_oracle)."""
+    (test_gpu_parity.py::test_c4_fold_mixed_radix_vs_oracle).  The launch plan
+    of each run must show the split named above and its kernels."""
     from psrsigsim_amd import _lib
+    from tests import replay
+    rows = shard[1] - shard[0] if shard else nchan
+    nsamp = int(round(tobs / 60.0)) * samprate_bins
+    split = FOLD_SPLITS[(tobs, samprate_bins)]
 
     def run():
         import psrsigsim_amd as pss
@@ -151,13 +160,19 @@ def test_fold_fast_bitwise_equals_generic(nchan, shard, tobs, samprate_bins, hip
         return sig.data.cpu().numpy()
 
     L = _lib.lib()
+    _lib.plan_collect()
     fast = run()
+    replay.assert_plan(_lib.plan_collect(), rows, nsamp, ("smooth", split, "A:fold", "C:fold"),
+                       absent=("A:generic", "C:generic"))
     assert np.isfinite(fast).all()
     old = L.pss_set_flags(_lib.FLAG_NO_FAST)
     try:
+        _lib.plan_collect()
         generic = run()
     finally:
         L.pss_set_flags(old)
+    replay.assert_plan(_lib.plan_collect(), rows, nsamp, ("smooth", split, "A:generic", "C:generic"),
+                       absent=("A:fold", "C:fold"))
     np.testing.assert_array_equal(fast, generic)
 
 

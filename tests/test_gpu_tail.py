@@ -31,8 +31,18 @@ def _a_of(sig, tau_d, ref):
     return np.exp(-sig._dt_ms() / tau_ms)
 
 
-@pytest.mark.parametrize("N", [1 << 16, 4096, 30720, 100002])
+def _assert_tail_plan(lines, nchan, N):
+    """The run took N's geometry (tests/fft_geometries.py, variant 2) and, on
+    the four-step splits, the tail row pass."""
+    from tests import fft_geometries, replay
+    g = fft_geometries.of_length(N, 2)
+    replay.assert_plan(lines, nchan, N, g.tokens + (("R:pair_row_tail",) if g.kind in ("fourstep", "smooth") else ()))
+
+
+# (2^15 = 16 x 2048: 2048-point rows; 49152 = 6 x 8192: 8192-point rows)
+@pytest.mark.parametrize("N", [1 << 16, 4096, 30720, 100002, 1 << 15, 49152])
 def test_tail_impulse_response_analytic(N, hip_lib):
+    from psrsigsim_amd import _lib
     from psrsigsim_amd.ism import ISM
     nchan = 3
     n0 = np.array([0, 17, N // 3])
@@ -41,8 +51,10 @@ def test_tail_impulse_response_analytic(N, hip_lib):
     sig = _signal(nchan, N, x)
     tau_d, ref = 2e-4, 1400.0
     a = _a_of(sig, tau_d, ref)
+    _lib.plan_collect()
     ISM().scatter_broaden(sig, tau_d, ref, tail=True)
     got = sig.data.cpu().numpy().astype(np.float64)
+    _assert_tail_plan(_lib.plan_collect(), nchan, N)
     assert sig.delay is None                         # a filter, not a delay
     for c in range(nchan):
         m = (np.arange(N) - n0[c]) % N
@@ -66,8 +78,9 @@ def _np_tail_delay(x, a, s):
     return np.fft.irfft(Y, n=N)
 
 
-@pytest.mark.parametrize("N", [1 << 16, 1 << 14, 4096, 100002])
+@pytest.mark.parametrize("N", [1 << 16, 1 << 14, 4096, 100002, 1 << 15, 49152])
 def test_tail_fused_with_dispersion(N, hip_lib):
+    from psrsigsim_amd import _lib
     from psrsigsim_amd.ism import ISM
     rng = np.random.default_rng(N)
     nchan = 4
@@ -79,7 +92,9 @@ def test_tail_fused_with_dispersion(N, hip_lib):
     from psrsigsim_amd.ism.ism import push_delay
     delays_ms = np.linspace(3.0, 9.0, nchan)           # a delay stage in the same fused pass
     push_delay(sig, delays_ms)
+    _lib.plan_collect()
     got = sig.data.cpu().numpy().astype(np.float64)
+    _assert_tail_plan(_lib.plan_collect(), nchan, N)
     s = delays_ms / sig._dt_ms()
     for c in range(nchan):
         ref = _np_tail_delay(x[c].astype(np.float32).astype(np.float64), a[c], s[c])

@@ -320,3 +320,84 @@ def test_native_pchip_long_rows_spans_bitwise(rows):
             _lib.check(L.pss_host_pchip_table(_lib._dptr(x), K, _lib._dptr(y), rows, h, amax, _lib._dptr(t), nt),
                        "table")
             np.testing.assert_array_equal(t, _lib.host_device_table(c_np, h, amax))
+
+
+# ---------------------------------------------------------------------------
+# the FFT plan classifier (pss_plan_geometry) and tests/fft_geometries.py
+# ---------------------------------------------------------------------------
+def _plan_sweep_lengths():
+    """Geometry depends only on the magnitude, the 2-adic valuation and the
+    odd part of N (fourstep_split, smooth_split: N1 = N / 2^m <= 60 or 1250;
+    bs_geom: the next power of two): every even N up to 2^18, above that every
+    c 2^v <= 2^24 with c odd < 128 (and 2^3 5^8), and 2^v +- 2 (the first and
+    last length of every Bluestein size)."""
+    ns = set(range(64, (1 << 18) + 1, 2))
+    for c in range(1, 128, 2):
+        n = 2 * c
+        while n <= (1 << 24):
+            if n >= 64:
+                ns.add(n)
+            n *= 2
+    for v in range(6, 25):
+        ns.update(n for n in ((1 << v) - 2, (1 << v) + 2) if 64 <= n <= (1 << 24))
+    ns.add(3125000)
+    return sorted(ns)
+
+
+def test_fft_geometry_table_is_complete():
+    """The set of (kind, N1, N2, variant) the classifier returns over the
+    sweep equals tests/fft_geometries.py, and each row's nsamp is the smallest
+    sweep length of its geometry -- so a geometry added to the dispatch
+    without a row there (and a GPU test with it) fails here."""
+    from psrsigsim_amd import _lib
+    from tests import fft_geometries as G
+    first = {}
+    for v in G.VARIANTS:
+        for n in _plan_sweep_lengths():
+            kind, n1, n2 = _lib.plan_geometry(n, v)
+            assert kind != "unsupported", (n, v)
+            first.setdefault((kind, n1, n2, v), n)
+    table = {(g.kind, g.n1, g.n2, g.variant): g for g in G.GEOMETRIES}
+    assert len(table) == len(G.GEOMETRIES), "duplicate rows"
+    assert set(first) == set(table), (sorted(set(first) - set(table)), sorted(set(table) - set(first)))
+    wrong = {k: (g.nsamp, first[k]) for k, g in table.items() if g.nsamp != first[k]}
+    assert not wrong, wrong
+    for g in G.GEOMETRIES:
+        for n in (g.nsamp,) + g.also:
+            assert _lib.plan_geometry(n, g.variant) == (g.kind, g.n1, g.n2), (g, n)
+
+
+def test_gpu_delay_sweeps_cover_the_table():
+    """The parity length sweep keeps its lengths (they are lengths of table
+    rows), so with the rest of the table's delay lengths (run by
+    tests/test_gpu_fft_geometries.py) every delay-only row runs on the GPU."""
+    from tests import fft_geometries as G
+    assert set(G.PARITY_SWEEP) <= set(G.delay_lengths()), set(G.PARITY_SWEEP) - set(G.delay_lengths())
+    assert {g.nsamp for g in G.rows(variant=0)} <= set(G.delay_lengths())
+
+
+def test_plan_geometry_edges_and_flags():
+    """Lengths run_paths never sees (validate rejects them) are UNSUPPORTED;
+    PSS_FLAG_DIRECT_DFT moves the Bluestein lengths, and only those, to the
+    direct DFT, as run_fallback does."""
+    from psrsigsim_amd import _lib
+    L = _lib.load()
+    for n in (0, -2, 63, 1001, (1 << 24) + 2):
+        assert _lib.plan_geometry(n, 0) == ("unsupported", 0, 0), n
+    assert _lib.plan_geometry(4096, 3)[0] == "unsupported"
+    assert L.pss_plan_geometry(1 << 20, 0, None, None) == _lib.PLAN_KINDS.index("fourstep")   # NULL outputs
+    assert _lib.plan_geometry(62, 0) == ("direct", 0, 0)
+    # a delayed null off the 2^m lengths runs on the packed paths
+    assert _lib.plan_geometry(6144, 1) == ("direct", 0, 0)
+    assert _lib.plan_geometry(30720, 1) == ("bluestein", 16, 4096)
+    assert _lib.plan_geometry(30720, 2) == ("smooth", 30, 1024)
+    old = L.pss_set_flags(_lib.FLAG_DIRECT_DFT)
+    try:
+        assert _lib.plan_geometry(10006, 0) == ("direct", 0, 0)
+        assert _lib.plan_geometry(30720, 1) == ("direct", 0, 0)
+        assert _lib.plan_geometry(30720, 0) == ("smooth", 30, 1024)
+        assert _lib.plan_geometry(1 << 20, 1) == ("fourstep", 256, 4096)
+        assert _lib.plan_geometry(4096, 0) == ("single", 1, 4096)
+    finally:
+        L.pss_set_flags(old)
+    assert _lib.plan_geometry(10006, 0) == ("bluestein", 8, 4096)
