@@ -515,6 +515,49 @@ int pss_harmonic_search(const float *spec, int32_t ndm, int64_t nbin, int64_t ld
                         int32_t nl, int64_t kmin, int32_t cell, float *snr, int32_t *code, int64_t out_ld,
                         float *work, void *stream);
 
+/*
+ * Fold of dedispersed series at fractional periods (extension, no reference
+ * counterpart): the phase x time cube of periodicity candidates.  x[nser][ld]
+ * float32 holds T samples per row; src[nrows] (int32), inc[nrows] and
+ * phi0[nrows] (uint64) are device tables, phi0 may be NULL (all zero).  Output
+ * row r folds one series at its own period into nsub sub-integrations of L
+ * samples and nbin phase bins.  Phases are 64-bit fixed point, a turn is 2^64,
+ * all arithmetic on them wrapping uint64 -- no floating point enters a bin:
+ *   inc        = floor(2^64 / Ps + 1/2)        (the caller's; Ps the period in samples)
+ *   i(r)       = min(max(src[r], 0), nser - 1)
+ *   inc(r)     = min(inc[r], floor(2^64 / nbin))            (Ps >= nbin)
+ *   phi_r(u)   = (phi0[r] + u * inc(r)) mod 2^64            u = 0, 1, 2 ..
+ *   bin_r(u)   = ((phi_r(u) >> 32) * nbin) >> 32            in [0, nbin), any nbin
+ *   out [(r * nsub + s) * nbin + b] = float32(sum of x[i(r) * ld + u] over
+ *                                     s L <= u < (s + 1) L with bin_r(u) = b)
+ *   hits[(r * nsub + s) * nbin + b] = the number of such u  (int32; hits may be NULL)
+ * for r < nrows, s < nsub, b < nbin; both outputs are contiguous
+ * [nrows][nsub][nbin], and a bin without a sample holds 0.  Samples at
+ * u >= nsub * L are not read.  A sum is accumulated in float64 and rounded to
+ * float32 once.  A workgroup owns one (r, s); a bin's samples are added in the
+ * order of u by one thread when nbin > 128, and otherwise by G = floor(256 /
+ * nbin) threads whose partial sums are then added in the order g = 0 .. G - 1.
+ * With n = floor(2^64 / inc(r)): for n <= floor(4096 / G) and for n >= 2^40
+ * thread g takes the turns g, g + G, .. of the bin, counted from the
+ * sub-integration's first sample (a run of the bin already under way there
+ * goes to g = 0); in between it takes the samples g q <= i < (g + 1) q of
+ * every run of the bin, i counted from the run's first sample (which may lie
+ * before the sub-integration), q = ceil((1 + floor(Wmax / inc(r))) / G), Wmax
+ * = ceil(2^32 / nbin) 2^32.  That order is a function of (L, nbin, inc(r),
+ * phi_r(s L)) alone, so the bits depend on neither the run, the alignment of
+ * x / ld / out, the position of the row in the table nor the other rows of the
+ * call.  No atomics, no workspace; nothing is written outside out / hits, and
+ * because of the two clamps no read leaves [0, nsub * L) of a row of x
+ * whatever the tables hold (inc = 0 is valid: every sample falls in the bin of
+ * phi0).
+ * PSS_EINVAL (nothing launched) on a NULL x / src / inc / out, nser < 1,
+ * nrows < 1, nsub < 1, L < 1, nsub * L > T, ld < T, nbin outside [2, 1024],
+ * and when nrows * nsub exceeds 2^31 - 1 (the launch grid).
+ */
+int pss_fold_series(const float *x, int32_t nser, int64_t T, int64_t ld, const int32_t *src,
+                    const uint64_t *inc, const uint64_t *phi0, int32_t nrows, int32_t nsub, int64_t L,
+                    int32_t nbin, float *out, int32_t *hits, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,8 +2,8 @@
 // pss_common.hpp -- what every unit of the library needs and nothing else:
 // error reporting, the launch checks and the small host / device helpers the
 // stand-alone stages (pss_searchout, pss_channelize, pss_dedisperse,
-// pss_boxsearch, pss_harmsum) share with the synthesis engine.  See include/pss_hip.h for
-// the ABI.
+// pss_boxsearch, pss_harmsum, pss_foldseries) share with the synthesis engine.
+// See include/pss_hip.h for the ABI.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
