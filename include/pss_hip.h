@@ -558,6 +558,52 @@ int pss_fold_series(const float *x, int32_t nser, int64_t T, int64_t ld, const i
                     const uint64_t *inc, const uint64_t *phi0, int32_t nrows, int32_t nsub, int64_t L,
                     int32_t nbin, float *out, int32_t *hits, void *stream);
 
+/*
+ * Time-domain resampling of dedispersed series for trial accelerations
+ * (extension, no reference counterpart): the first stage of an acceleration
+ * search.  x[nser][ld] float32 holds T samples per row; src[nrows] (int32),
+ * kappa[nrows] (int64) and sub[nrows] (float32; may be NULL) are device tables.
+ * Output row r is series i(r) read at the quadratically stretched times
+ * t + alpha t (T - t), alpha = kappa / 2^64 per sample -- integers only, no
+ * floating point enters an index:
+ *   i(r)     = min(max(src[r], 0), nser - 1)
+ *   K(r)     = min(|kappa[r]|, floor(2^63 / T))      (the magnitude taken in
+ *                                  uint64), sg(r) = -1 if kappa[r] < 0, else +1
+ *   u(t)     = t (T - t)            (T, not n_out: cutting the output short does
+ *                                    not change the map)
+ *   s_r(t)   = (u(t) K(r) + 2^63) >> 64      the 128-bit product, rounded half up
+ *   idx_r(t) = min(max(t + sg(r) s_r(t), 0), T - 1)
+ *   out[r * out_ld + t] = x[i(r) * ld + idx_r(t)] - sub[r]      t < n_out, r < nrows
+ * The subtraction is one rounded float32 operation; with sub == NULL the bits
+ * are copied (a NaN's payload and -0.0 included).  kappa is the caller's
+ * alpha 2^64 in fixed point, |alpha| = 4 |s_max| / T^2 for a shift of s_max
+ * samples at mid-observation.
+ * Bounds.  The clamp of K is alpha T <= 1/2.  With f(t) = u(t) K / 2^64 (a
+ * real number), f(t + 1) - f(t) = K (T - 2 t - 1) / 2^64 lies in (-1/2, 1/2),
+ * and s = floor(f + 1/2) of two numbers less than 1/2 apart differs by 0, or
+ * by 1 in the direction of the difference: s steps by -1, 0 or 1 and idx_r,
+ * which adds the step 1 of t, by 0, 1 or 2 -- it is non-decreasing.  u(0) = 0
+ * gives idx_r(0) = 0, and f(T - 1) = K (T - 1) / 2^64 < 1/2 gives s = 0 and
+ * idx_r(T - 1) = T - 1.  So idx_r runs from 0 to T - 1 without ever leaving
+ * [0, T): the index clamp never acts.  It stays in the definition so that no
+ * table can make a read leave [0, T) of a row; nothing is written outside
+ * out[r * out_ld + 0 .. n_out).  T <= 2^31 - 1 keeps u below 2^62.
+ * A workgroup owns 2048 output times of 8 consecutive rows.  The rows among
+ * them that read the series of the first and whose source samples fit one
+ * window of 4096 floats are served from a copy of that window in LDS, read
+ * from global memory once; any other row gathers from global memory.  Every
+ * output is one word of x by either route: no atomics, no workspace, and the
+ * bits depend on neither the alignment of x / ld / out / out_ld, the position
+ * of the row in the table, the other rows of the call nor the run.
+ * PSS_EINVAL (nothing launched) on a NULL x / src / kappa / out, nser < 1,
+ * nrows < 1, T < 1, T > 2^31 - 1, ld < T, n_out < 1, n_out > T,
+ * out_ld < n_out, and when ceil(n_out / 2048) * ceil(nrows / 8) exceeds
+ * 2^31 - 1 (the launch grid).
+ */
+int pss_accel_resample(const float *x, int32_t nser, int64_t T, int64_t ld, const int32_t *src,
+                       const int64_t *kappa, const float *sub, int32_t nrows, int64_t n_out, float *out,
+                       int64_t out_ld, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
