@@ -109,17 +109,24 @@ def device():
     return torch.device("cuda", torch.cuda.current_device())
 
 
-def stream_ptr():
-    """The launch stream for a library call; it first waits (on the device)
-    for the uploads to_dev queued since the last call -- one event per call,
-    not one per table."""
+def wait_uploads():
+    """The upload fence: the launch stream waits (on the device) for the
+    uploads to_dev queued since the last fence -- one event per fence, not
+    one per table; nothing pending, nothing done.  Every library call passes
+    it (stream_ptr); a torch op that reads an uploaded table before the next
+    library call needs it in front.  Returns the launch stream."""
     st = torch.cuda.current_stream()
     if _upload_pending:
         idx = st.device.index
         if idx in _upload_pending:
             st.wait_stream(_upload[idx])
             _upload_pending.discard(idx)
-    return ctypes.c_void_p(st.cuda_stream)
+    return st
+
+
+def stream_ptr():
+    """The launch stream for a library call, past the upload fence."""
+    return ctypes.c_void_p(wait_uploads().cuda_stream)
 
 
 _ws = {}

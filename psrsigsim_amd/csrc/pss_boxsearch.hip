@@ -30,7 +30,8 @@
 //       (t + 2^k <= T), so no padding value ever reaches a result.  A thread
 //       keeps the best (z, k) of each of its start times (strict >, k rising:
 //       ties stay with the narrower width; a NaN never compares greater).
-//       The cells: (z, code) of the 2048 start times go to LDS, thread i scans
+//       The cells (cm_reduce_store, pss_cellmax.hpp, shared with
+//       pss_harmsum.hip): (z, code) of the 2048 start times go to LDS, thread i scans
 //       the 8 consecutive times 8 i .. 8 i + 7 (one cell holds them all: cell is
 //       a multiple of 16), then cell / 8 neighbouring threads combine by a
 //       butterfly of wave shuffles (and, for cell >= 1024, across the waves
@@ -43,30 +44,19 @@
 //       Logical workgroup index = trial * tiles + tile, dealt to the XCDs in
 //       contiguous runs (as k_dedisperse): neighbouring tiles, which share a
 //       halo, read it through one L2.
-#include "pss_common.hpp"
+#include "pss_cellmax.hpp"
 
 using namespace pss;
 
-static constexpr int kBsThreads = 256;
-static constexpr int kBsOwn = 8;                          // start times per lane
-static constexpr int kBsTile = kBsThreads * kBsOwn;       // start times per workgroup
+static constexpr int kBsThreads = kCmThreads;
+static constexpr int kBsOwn = kCmOwn;                     // start times per lane
+static constexpr int kBsTile = kCmTile;                   // start times per workgroup
 static constexpr int kBsMaxW = 13;                        // widths 2^0 .. 2^12
 
 struct BoxArgs {
     int64_t T, ld, out_ld, nq, ntiles;
     int32_t ndm, nw, cell, lcell;
 };
-
-// a_k = 2^-ceil(k/2) * (k odd ? fp32(sqrt 2) : 1): exact scalings of 0x3FB504F3
-__device__ __forceinline__ float bs_coef(int k) {
-    const float s = (k & 1) ? __uint_as_float(0x3FB504F3u) : 1.0f;
-    return s * __uint_as_float((uint32_t)(127 - ((k + 1) >> 1)) << 23);
-}
-
-// "a beats b": larger z, then the smaller code (narrower width, then earlier time)
-__device__ __forceinline__ bool bs_better(float za, int ca, float zb, int cb) {
-    return za > zb || (za == zb && ca < cb);
-}
 
 // y[e] = row[e] - mean for e < valid = min(256 NI, samples left in the row),
 // 0 for valid <= e < 256 (NI + 1) -> w[e]
@@ -165,7 +155,7 @@ __global__ __launch_bounds__(kBsThreads) void k_boxcar_search(const float *__res
 #pragma unroll
     for (int k = 0; k < kNW; ++k) {
         if (k < nw) {                                      // (wave-uniform)
-            const float c = bs_coef(k) * rs;
+            const float c = cm_coef(k) * rs;
 #pragma unroll
             for (int i = 0; i < kBsOwn; ++i) {
                 const float z = S[i] * c;
@@ -204,74 +194,10 @@ __global__ __launch_bounds__(kBsThreads) void k_boxcar_search(const float *__res
         }
     }
 
-    // per-cell reduction: (z, code) of the tile's start times through LDS
+    // per-cell reduction (pss_cellmax.hpp): the window is free once every thread has read its partners
     __syncthreads();
-    int *wcode = reinterpret_cast<int *>(win + kBsTile);
-    const int cmask = a.cell - 1;
-#pragma unroll
-    for (int i = 0; i < kBsOwn; ++i) {
-        const int e = tid + i * kBsThreads;
-        win[e] = bz[i];
-        wcode[e] = (bk[i] << 16) | (e & cmask);
-    }
-    __syncthreads();
-    float rz;
-    int rc;
-    {
-        const float4 z0 = *reinterpret_cast<const float4 *>(win + 8 * tid);
-        const float4 z1 = *reinterpret_cast<const float4 *>(win + 8 * tid + 4);
-        const int4 c0 = *reinterpret_cast<const int4 *>(wcode + 8 * tid);
-        const int4 c1 = *reinterpret_cast<const int4 *>(wcode + 8 * tid + 4);
-        const float zz[8] = {z0.x, z0.y, z0.z, z0.w, z1.x, z1.y, z1.z, z1.w};
-        const int cc[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
-        rz = zz[0];
-        rc = cc[0];
-#pragma unroll
-        for (int i = 1; i < 8; ++i)
-            if (bs_better(zz[i], cc[i], rz, rc)) {
-                rz = zz[i];
-                rc = cc[i];
-            }
-    }
-    const int tpc = a.cell >> 3;                           // threads per cell: 2 .. 256
-    for (int off = 1; off < min(tpc, 64); off <<= 1) {
-        const float oz = __shfl_xor(rz, off);
-        const int oc = __shfl_xor(rc, off);
-        if (bs_better(oz, oc, rz, rc)) {
-            rz = oz;
-            rc = oc;
-        }
-    }
-    int qc = tid >> (a.lcell - 3);                                  // the tile's cell of this thread
-    bool writer = (tid & (tpc - 1)) == 0;
-    if (tpc > 64) {                                        // (uniform) cell 1024 or 2048: across the waves
-        if ((tid & 63) == 0) {
-            redz[tid >> 6] = rz;
-            redc[tid >> 6] = rc;
-        }
-        __syncthreads();
-        const int wpc = tpc >> 6;                          // waves per cell: 2 or 4
-        writer = tid < kBsThreads / tpc;
-        qc = tid;
-        if (writer) {
-            rz = redz[tid * wpc];
-            rc = redc[tid * wpc];
-            for (int w = 1; w < wpc; ++w) {
-                const float oz = redz[tid * wpc + w];
-                const int oc = redc[tid * wpc + w];
-                if (bs_better(oz, oc, rz, rc)) {
-                    rz = oz;
-                    rc = oc;
-                }
-            }
-        }
-    }
-    const int64_t q = (t0 >> a.lcell) + qc;
-    if (writer && q < a.nq) {
-        PSS_DASSERT(q >= 0 && q < a.out_ld);
-        snr[(int64_t)j * a.out_ld + q] = rz;
-        code[(int64_t)j * a.out_ld + q] = rz == -INFINITY ? 0 : rc;
-    }
+    cm_reduce_store(win, reinterpret_cast<int *>(win + kBsTile), redz, redc, bz, bk, tid, a.cell, a.lcell,
+                    t0 >> a.lcell, a.nq, j, a.out_ld, snr, code);
 }
 
 template <int HB>

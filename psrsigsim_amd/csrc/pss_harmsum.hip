@@ -39,20 +39,21 @@
 //       leaves [kmin, nbin) of the row.
 //       A thread keeps the best (z, l) of each of its bins (strict >, l rising:
 //       ties stay with the lower level; a NaN never compares greater).  The
-//       cells are reduced as in pss_boxsearch.hip: (z, code) of the 2048 bins go
+//       cells are reduced as in pss_boxsearch.hip (cm_reduce_store,
+//       pss_cellmax.hpp, shared by the two): (z, code) of the 2048 bins go
 //       to LDS, thread i scans the bins 8 i .. 8 i + 7, then cell / 8
 //       neighbouring threads combine by a butterfly of wave shuffles (and, for
 //       cell >= 1024, across the waves through LDS) under the total order
 //       "larger z, then smaller code" -- code = l << 16 | k - q cell.  One
 //       thread per cell stores snr and code as dwords.  No atomics; the bits
 //       depend on neither the alignment, the workspace nor the launch geometry.
-#include "pss_common.hpp"
+#include "pss_cellmax.hpp"
 
 using namespace pss;
 
-static constexpr int kHsThreads = 256;
-static constexpr int kHsOwn = 8;                          // bins per lane
-static constexpr int kHsTile = kHsThreads * kHsOwn;       // bins per workgroup
+static constexpr int kHsThreads = kCmThreads;
+static constexpr int kHsOwn = kCmOwn;                     // bins per lane
+static constexpr int kHsTile = kCmTile;                   // bins per workgroup
 static constexpr int kHsMaxL = 5;                         // levels: 1, 2, 4, 8, 16 harmonics
 static constexpr int64_t kHsMaxBin = (int64_t)1 << 27;    // k * 16 + 8 in 31 bits
 
@@ -60,17 +61,6 @@ struct HarmArgs {
     int64_t nbin, ld, out_ld, nq, ntiles, kmin;
     int32_t ndm, nl, cell, lcell;
 };
-
-// a_l = 2^-ceil(l/2) * (l odd ? fp32(sqrt 2) : 1): exact scalings of 0x3FB504F3
-__device__ __forceinline__ float hs_coef(int l) {
-    const float s = (l & 1) ? __uint_as_float(0x3FB504F3u) : 1.0f;
-    return s * __uint_as_float((uint32_t)(127 - ((l + 1) >> 1)) << 23);
-}
-
-// "a beats b": larger z, then the smaller code (lower level, then lower bin)
-__device__ __forceinline__ bool hs_better(float za, int ca, float zb, int cb) {
-    return za > zb || (za == zb && ca < cb);
-}
 
 // where the terms come from
 enum : int { kHsElem = 0, kHsVec = 1, kHsPow = 2 };
@@ -172,7 +162,7 @@ __global__ __launch_bounds__(kHsThreads) void k_harmonic_search(const float *__r
 #pragma unroll
                 for (int i = 0; i < kHsOwn; ++i) H[i] = l == 0 ? p[i] : __fadd_rn(H[i], p[i]);
             }
-            const float c = hs_coef(l);
+            const float c = cm_coef(l);
             const float h = (float)(1 << l);
 #pragma unroll
             for (int i = 0; i < kHsOwn; ++i) {
@@ -185,72 +175,9 @@ __global__ __launch_bounds__(kHsThreads) void k_harmonic_search(const float *__r
         }
     }
 
-    // per-cell reduction: (z, code) of the tile's bins through LDS
-    const int cmask = a.cell - 1;
-#pragma unroll
-    for (int i = 0; i < kHsOwn; ++i) {
-        const int e = tid + i * kHsThreads;
-        wz[e] = bz[i];
-        wcode[e] = (bl[i] << 16) | (e & cmask);
-    }
-    __syncthreads();
-    float rz;
-    int rc;
-    {
-        const float4 z0 = *reinterpret_cast<const float4 *>(wz + 8 * tid);
-        const float4 z1 = *reinterpret_cast<const float4 *>(wz + 8 * tid + 4);
-        const int4 c0 = *reinterpret_cast<const int4 *>(wcode + 8 * tid);
-        const int4 c1 = *reinterpret_cast<const int4 *>(wcode + 8 * tid + 4);
-        const float zz[8] = {z0.x, z0.y, z0.z, z0.w, z1.x, z1.y, z1.z, z1.w};
-        const int cc[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
-        rz = zz[0];
-        rc = cc[0];
-#pragma unroll
-        for (int i = 1; i < 8; ++i)
-            if (hs_better(zz[i], cc[i], rz, rc)) {
-                rz = zz[i];
-                rc = cc[i];
-            }
-    }
-    const int tpc = a.cell >> 3;                           // threads per cell: 2 .. 256
-    for (int off = 1; off < min(tpc, 64); off <<= 1) {
-        const float oz = __shfl_xor(rz, off);
-        const int oc = __shfl_xor(rc, off);
-        if (hs_better(oz, oc, rz, rc)) {
-            rz = oz;
-            rc = oc;
-        }
-    }
-    int qc = tid >> (a.lcell - 3);                         // the tile's cell of this thread
-    bool writer = (tid & (tpc - 1)) == 0;
-    if (tpc > 64) {                                        // (uniform) cell 1024 or 2048: across the waves
-        if ((tid & 63) == 0) {
-            redz[tid >> 6] = rz;
-            redc[tid >> 6] = rc;
-        }
-        __syncthreads();
-        const int wpc = tpc >> 6;                          // waves per cell: 2 or 4
-        writer = tid < kHsThreads / tpc;
-        qc = tid;
-        if (writer) {
-            rz = redz[tid * wpc];
-            rc = redc[tid * wpc];
-            for (int w = 1; w < wpc; ++w) {
-                const float oz = redz[tid * wpc + w];
-                const int oc = redc[tid * wpc + w];
-                if (hs_better(oz, oc, rz, rc)) {
-                    rz = oz;
-                    rc = oc;
-                }
-            }
-        }
-    }
-    const int64_t q = (int64_t)(k0 >> a.lcell) + qc;
-    if (writer && q < a.nq) {
-        PSS_DASSERT(q >= 0 && q < a.out_ld);
-        snr[(int64_t)j * a.out_ld + q] = rz;
-        code[(int64_t)j * a.out_ld + q] = rz == -INFINITY ? 0 : rc;
-    }
+    // per-cell reduction (pss_cellmax.hpp)
+    cm_reduce_store(wz, wcode, redz, redc, bz, bl, tid, a.cell, a.lcell, (int64_t)(k0 >> a.lcell), a.nq, j, a.out_ld,
+                    snr, code);
 }
 
 extern "C" {

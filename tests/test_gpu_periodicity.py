@@ -136,8 +136,8 @@ def same_bits(a, b):
     return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
-EXACT = [("r2500", 16), ("r2500", 2048), ("edges", 32), ("edge-1", 32), ("edge+1", 32), ("edge+1", 2048),
-         ("s1_1", 16), ("s1_3", 16), ("s7_1", 16), ("s7_3", 16), ("s17_1", 16), ("s17_3", 16),
+EXACT = [("r2500", 16), ("r2500", 2048), ("edges", 32), ("edge-1", 32), ("edge+1", 32), ("edge+1", 512),
+         ("edge+1", 2048), ("s1_1", 16), ("s1_3", 16), ("s7_1", 16), ("s7_3", 16), ("s17_1", 16), ("s17_3", 16),
          ("kmin700", 32), ("kmin700", 1024), ("trials", 32), ("plateau", 32), ("plateau_k5", 256),
          ("r2500_nl1", 32), ("r2500_nl2", 32), ("r2500_nl3", 32), ("r2500_nl4", 32)]
 

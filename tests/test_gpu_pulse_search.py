@@ -109,7 +109,8 @@ def same_bits(a, b):
 
 
 EXACT = [("one", 16), ("ragged", 32), ("t2049", 32), ("t2047", 32), ("plateau", 32)] + \
-        [(n, c) for n in ("t2049", "t2047", "plateau") for c in (16, 256, 2048)]
+        [(n, c) for n in ("t2049", "t2047", "plateau") for c in (16, 256, 2048)] + \
+        [("t2049", 512), ("t2049", 1024)]      # exactly one wave per cell, and two (the shared cell reduction)
 
 
 @pytest.mark.parametrize("name,cell", EXACT)

@@ -36,13 +36,14 @@ the median of --reps calls (min and max are kept).  Needs the GPU: there is no
 CPU path.
 """
 import argparse
-import json
+import functools
 import os
 import sys
 from fractions import Fraction
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+import bench_util  # noqa: E402  (tools/, next to this file)
 
 VARIANT, VARIANT_FLAGS = "accel_nostage", ["-DPSS_ACCEL_NO_STAGE=1"]
 TILES = (("1024", "accel_tb1024", ["-DPSS_ACCEL_RUNS=1"]), ("4096", "accel_tb4096", ["-DPSS_ACCEL_RUNS=4"]))
@@ -86,18 +87,7 @@ def main():
     nser, nacc, cell = args.nser, args.nacc, args.cell
     rows = nser * nacc
 
-    def timed(fn):
-        fn()                                         # warm-up (code object load, first touch, allocator, FFT plan)
-        ms = []
-        for _ in range(args.reps):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            b.synchronize()
-            ms.append(a.elapsed_time(b))
-        ms.sort()
-        return {"ms": round(ms[len(ms) // 2], 4), "min_ms": round(ms[0], 4), "max_ms": round(ms[-1], 4)}
+    timed = functools.partial(bench_util.timed, reps=args.reps)
 
     res = {"reps": args.reps, "device": torch.cuda.get_device_name(dev), "library": os.path.basename(_lib.LIB_PATH),
            "direct_library": "libpss_hip_%s.so (%s)" % (VARIANT, " ".join(VARIANT_FLAGS)), "rows": []}
@@ -199,12 +189,7 @@ def main():
         res["rows"].append(e)
         del x, out, spec, snr, code, work
         torch.cuda.empty_cache()
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    bench_util.emit(res, args.out)
 
 
 if __name__ == "__main__":

@@ -21,11 +21,12 @@ the median of --reps calls (min and max are kept).  additions = C * T * ndm, the
 adds of the direct sum.  Needs the GPU: there is no CPU path.
 """
 import argparse
-import json
+import functools
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import bench_util  # noqa: E402  (tools/, next to this file)
 
 
 def main():
@@ -47,18 +48,7 @@ def main():
     dev = torch.device("cuda", torch.cuda.current_device())
     st = torch.cuda.current_stream().cuda_stream
 
-    def timed(fn):
-        fn()                                         # warm-up (code object load, first touch, allocator)
-        ms = []
-        for _ in range(args.reps):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            b.synchronize()
-            ms.append(a.elapsed_time(b))
-        ms.sort()
-        return {"ms": round(ms[len(ms) // 2], 4), "min_ms": round(ms[0], 4), "max_ms": round(ms[-1], 4)}
+    timed = functools.partial(bench_util.timed, reps=args.reps)
 
     res = {"reps": args.reps, "device": torch.cuda.get_device_name(dev), "shapes": []}
     dms = np.linspace(0.0, 100.0, args.ndm)
@@ -110,12 +100,7 @@ def main():
         res["shapes"].append(e)
         del x, out, comp_out, t, tab64
         torch.cuda.empty_cache()
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    bench_util.emit(res, args.out)
 
 
 if __name__ == "__main__":

@@ -33,12 +33,13 @@ agree bit for bit (snr_equals_composition, code_equals_composition).  Needs
 the GPU: there is no CPU path.
 """
 import argparse
-import json
+import functools
 import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+import bench_util  # noqa: E402  (tools/, next to this file)
 
 
 def main():
@@ -61,18 +62,7 @@ def main():
     st = torch.cuda.current_stream().cuda_stream
     cell, ndm = args.cell, args.ndm
 
-    def timed(fn):
-        fn()                                         # warm-up (code object load, first touch, allocator, FFT plan)
-        ms = []
-        for _ in range(args.reps):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            b.synchronize()
-            ms.append(a.elapsed_time(b))
-        ms.sort()
-        return {"ms": round(ms[len(ms) // 2], 4), "min_ms": round(ms[0], 4), "max_ms": round(ms[-1], 4)}
+    timed = functools.partial(bench_util.timed, reps=args.reps)
 
     res = {"reps": args.reps, "device": torch.cuda.get_device_name(dev), "cell": cell,
            "library": os.path.basename(_lib.LIB_PATH), "rows": []}
@@ -166,12 +156,7 @@ def main():
             res["rows"].append(e)
         del x, snr, code, spec, work
         torch.cuda.empty_cache()
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    bench_util.emit(res, args.out)
 
 
 if __name__ == "__main__":

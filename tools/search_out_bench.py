@@ -15,11 +15,12 @@ HBM peak bench.py uses.  The grid is filled with the library's own chi2(1)
 draws.  Needs the GPU: there is no CPU path.
 """
 import argparse
-import json
+import functools
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import bench_util  # noqa: E402  (tools/, next to this file)
 
 HBM_PEAK_GBS = 8000.0
 
@@ -42,18 +43,7 @@ def main():
     dev = torch.device("cuda", torch.cuda.current_device())
     st = torch.cuda.current_stream().cuda_stream
 
-    def timed(fn):
-        fn()                                         # warm-up (code object load, first touch)
-        ms = []
-        for _ in range(args.reps):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            b.synchronize()
-            ms.append(a.elapsed_time(b))
-        ms.sort()
-        return {"ms": round(ms[len(ms) // 2], 4), "min_ms": round(ms[0], 4), "max_ms": round(ms[-1], 4)}
+    timed = functools.partial(bench_util.timed, reps=args.reps)
 
     def rate(entry, nbytes):
         entry["alg_bytes"] = nbytes
@@ -92,12 +82,7 @@ def main():
     res["quantize_tmajor"] = rate(timed(quant), grid_bytes + out_bytes)
     for k in ("chan_stats", "quantize_tmajor"):
         res[k]["vs_copy_rate"] = round(res[k]["GBps"] / res["device_copy"]["GBps"], 3)
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    bench_util.emit(res, args.out)
 
 
 if __name__ == "__main__":
