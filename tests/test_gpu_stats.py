@@ -212,9 +212,10 @@ def test_pulse_and_noise_moments_vs_oracle(hip_lib):
 def test_search_pulse_draws_are_chi2_1(hip_lib):
     """make_pulses alone (no delay): data / PCHIP(phase) ~ chi2(1), on the
     on-pulse samples of eight seeds pooled (8 x 61 486: one KS test, p >
-    0.01, and the mean).  The device stream is reproduced bit for bit by the
-    NumPy model in tools/philox_model.py, whose 400-seed study of this very
-    statistic (profiles/r03/philox_quality.txt) shows uniform p-values for
+    0.01, and the mean).  The device stream follows the NumPy model of
+    tests/philox_ref.py draw for draw (tests/test_gpu_draw_streams.py), and
+    the 400-seed study of this very statistic by tools/philox_model.py
+    (profiles/r03/philox_quality.txt) shows uniform p-values for
     Philox4x32-7 as for -10."""
     import psrsigsim_amd as pss
     from psrsigsim_amd.signal import FilterBankSignal
