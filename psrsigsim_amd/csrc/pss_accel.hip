@@ -23,10 +23,10 @@
 //         staged  (i(r) = i0 and the range ends inside the window of kAcWin =
 //                 4096 floats that begins at wlo, moved down to the 16-B grid
 //                 of the address): the window is copied to LDS once for all
-//                 such rows -- 16-B loads where the window's whole 16-B groups
-//                 lie inside [0, T) of the row, all issued before the first
-//                 LDS store; element loads where a group straddles the row's
-//                 ends -- and the outputs are gathered from LDS;
+//                 such rows (stage_window, pss_window.hpp: 16-B loads where
+//                 the window's whole 16-B groups lie inside [0, T) of the
+//                 row, element loads where a group straddles the row's
+//                 ends) and the outputs are gathered from LDS;
 //         direct  (another series, or a range past the window): the outputs
 //                 are gathered from global memory.
 //       The values are the same by either route: every output is one word of
@@ -41,6 +41,7 @@
 //       4096 times and windows of twice that (tools/accel_bench.py; DESIGN.md
 //       section 9).  The product is built with neither.
 #include "pss_common.hpp"
+#include "pss_window.hpp"
 
 using namespace pss;
 
@@ -56,7 +57,6 @@ static constexpr int kAcWin = 2 * kAcTB;                  // staged window, floa
 // a row's own range always fits: idx steps by at most 2, but over a tile by at
 // most len + (s(t0 + len - 1) - s(t0)) <= len + len / 2 + 1, plus 3 to the grid
 static_assert(kAcTB + kAcTB / 2 + 1 + 3 <= kAcWin, "a single row fits the window");
-static_assert(kAcWin % (4 * kAcThreads) == 0, "whole passes of 16-B loads");
 
 struct AcArgs {
     int64_t ld, out_ld;
@@ -87,42 +87,6 @@ __device__ __forceinline__ uint64_t ac_step(int64_t kappa, uint64_t kmax, int &s
     return min(mag, kmax);
 }
 
-// row[wb .. wb + need) -> w[0 .. need); row + wb is on the 16-B grid of the
-// address (wb itself may be as low as -3).  Words outside [0, T) of the row
-// are never needed and are zeros.
-__device__ __forceinline__ void ac_stage(uint32_t *w, const uint32_t *row, int64_t wb, int need, int32_t T, int tid) {
-    PSS_DASSERT(need >= 1 && need <= kAcWin && wb >= -3 && wb + need <= T);
-    const int nq = (need + 3) >> 2;                     // 16-B groups, <= kAcWin / 4
-    if (wb >= 0 && wb + 4 * (int64_t)nq <= T) {
-        // every group inside the row: the loads of all passes are issued,
-        // unconditionally, before the first LDS store waits for one.  The
-        // lanes past the last group re-load it (in bounds); a pass with work
-        // stores every lane's value, the copies in slots no output reads.
-        constexpr int NP = kAcWin / 4 / kAcThreads;
-        const uint4 *src = reinterpret_cast<const uint4 *>(row + wb);
-        uint4 v[NP];
-#pragma unroll
-        for (int i = 0; i < NP; ++i) v[i] = src[min(tid + i * kAcThreads, nq - 1)];
-#pragma unroll
-        for (int i = 0; i < NP; ++i) asm volatile("" : "+v"(v[i].x), "+v"(v[i].y), "+v"(v[i].z), "+v"(v[i].w));
-#pragma unroll
-        for (int i = 0; i < NP; ++i)
-            if (i * kAcThreads < nq) *reinterpret_cast<uint4 *>(w + 4 * (tid + i * kAcThreads)) = v[i];
-        return;
-    }
-    // the window's head or tail leaves the row by part of a 16-B group (the
-    // row's first or last tile): element loads
-    for (int q = tid; q < nq; q += kAcThreads) {
-        const int64_t s = wb + 4 * q;
-        uint4 v;
-        v.x = s >= 0 && s < T ? row[s] : 0u;
-        v.y = s + 1 >= 0 && s + 1 < T ? row[s + 1] : 0u;
-        v.z = s + 2 >= 0 && s + 2 < T ? row[s + 2] : 0u;
-        v.w = s + 3 >= 0 && s + 3 < T ? row[s + 3] : 0u;
-        *reinterpret_cast<uint4 *>(w + 4 * q) = v;
-    }
-}
-
 template <bool OVEC>
 __global__ __launch_bounds__(kAcThreads) void k_accel_resample(const uint32_t *__restrict__ x,
                                                                const int32_t *__restrict__ src,
@@ -131,9 +95,9 @@ __global__ __launch_bounds__(kAcThreads) void k_accel_resample(const uint32_t *_
                                                                uint32_t *__restrict__ out, AcArgs a) {
     __shared__ __align__(16) uint32_t win[kAcWin];
     const int tid = threadIdx.x;
-    const unsigned lid = xcd_run_id();
-    const int g = (int)(lid % (unsigned)a.ngroups);
-    const int32_t t0 = (int32_t)(lid / (unsigned)a.ngroups) * kAcTB;
+    const uint2 id = xcd_run_pair((unsigned)a.ngroups);
+    const int g = (int)id.y;
+    const int32_t t0 = (int32_t)id.x * kAcTB;
     const int r0 = g * kAcNR;
     const int nr = min(kAcNR, a.nrows - r0);                   // rows of this group (>= 1)
     const int len = min(kAcTB, a.n_out - t0);                  // times of this tile (>= 1)
@@ -173,7 +137,8 @@ __global__ __launch_bounds__(kAcThreads) void k_accel_resample(const uint32_t *_
 #endif
     }
     if (need > 0) {
-        ac_stage(win, row0, wb, need, T, tid);
+        // (row0 + wb is on the 16-B grid by construction, VEC; wb may be as low as -3, HEAD)
+        stage_window<kAcThreads, kAcWin, true, true>(win, row0, wb, need, T, tid);
         __syncthreads();
     }
 
@@ -252,13 +217,11 @@ int pss_accel_resample(const float *x, int32_t nser, int64_t T, int64_t ld, cons
         return fail(PSS_EINVAL, "accel_resample: out_ld %lld < n_out %lld", (long long)out_ld, (long long)n_out);
     const int64_t ngroups = ((int64_t)nrows + kAcNR - 1) / kAcNR;
     const int64_t ntiles = (n_out + kAcTB - 1) / kAcTB;
-    if (ntiles > (int64_t)0x7fffffff / ngroups)
-        return fail(PSS_EINVAL, "accel_resample: %lld time tiles x %lld row groups exceed 2^31 - 1 workgroups",
-                    (long long)ntiles, (long long)ngroups);
+    const dim3 grid = grid_1d("accel_resample", ntiles, "time tiles", ngroups, "row groups");
+    if (!grid.x) return PSS_EINVAL;
     AcArgs a;
     a.ld = ld; a.out_ld = out_ld; a.T = (int32_t)T; a.n_out = (int32_t)n_out; a.nser = nser; a.nrows = nrows;
     a.ngroups = (int32_t)ngroups; a.kmax = ((uint64_t)1 << 63) / (uint64_t)T;
-    const dim3 grid((unsigned)(ntiles * ngroups));
     const uint32_t *xw = reinterpret_cast<const uint32_t *>(x);
     uint32_t *ow = reinterpret_cast<uint32_t *>(out);
     // 16-B stores need the output rows on the 16-B grid.  Same bits.

@@ -67,9 +67,8 @@ __device__ __forceinline__ void bs_stage(float *w, const float *row, int valid, 
     const int ng = (valid + 3) >> 2;                      // 16-B groups that hold a sample
     if (VEC && (valid & 3) == 0) {
         // every group whole and inside the row (all but a row's last tiles):
-        // the loads of all passes are issued before the first LDS store waits
-        // for one (dd_stage).  Lanes past the last group re-load it (in
-        // bounds) and store zeros.
+        // loads before stores, pinned, as stage_window (pss_window.hpp).
+        // Lanes past the last group re-load it (in bounds) and store zeros.
         constexpr int NP = (kAll / 4 + kBsThreads - 1) / kBsThreads;
         const float4 *src = reinterpret_cast<const float4 *>(row);
         float4 v[NP];
@@ -127,10 +126,9 @@ __global__ __launch_bounds__(kBsThreads) void k_boxcar_search(const float *__res
     PSS_DASSERT(a.nw >= 1 && a.nw <= kNW && (HB == 1 || a.nw == kNW));
 
     // workgroup id -> (trial, tile), tiles fastest, through the XCD run map
-    const unsigned lid = xcd_run_id();
-    const int j = (int)(lid / (unsigned)a.ntiles);
-    const int64_t tile = (int64_t)(lid % (unsigned)a.ntiles);
-    const int64_t t0 = tile * kBsTile;
+    const uint2 id = xcd_run_pair((unsigned)a.ntiles);
+    const int j = (int)id.x;
+    const int64_t t0 = (int64_t)id.y * kBsTile;
     PSS_DASSERT(j >= 0 && j < a.ndm && t0 < a.T);
     const float mu = mean[j];
     const float rs = rstd[j];
@@ -202,8 +200,7 @@ __global__ __launch_bounds__(kBsThreads) void k_boxcar_search(const float *__res
 
 template <int HB>
 static int bs_launch(const float *plane, const float *mean, const float *rstd, float *snr, int32_t *code,
-                     const BoxArgs &a, hipStream_t st) {
-    const dim3 grid((unsigned)(a.ntiles * a.ndm));
+                     const BoxArgs &a, dim3 grid, hipStream_t st) {
     // 16-B loads of the window need the rows on the 16-B grid.  Same bits.
     if (on_grid16(plane, a.ld))
         k_boxcar_search<HB, true><<<grid, dim3(kBsThreads), 0, st>>>(plane, mean, rstd, snr, code, a);
@@ -226,27 +223,24 @@ int pss_boxcar_search(const float *plane, int32_t ndm, int64_t T, int64_t ld, co
     if (T < 1) return fail(PSS_EINVAL, "boxcar_search: T %lld < 1", (long long)T);
     if (ld < T) return fail(PSS_EINVAL, "boxcar_search: ld %lld < T %lld", (long long)ld, (long long)T);
     if (nw < 1 || nw > kBsMaxW) return fail(PSS_EINVAL, "boxcar_search: nw %d outside [1, %d]", nw, kBsMaxW);
-    if (cell < 16 || cell > kBsTile || (cell & (cell - 1)))
-        return fail(PSS_EINVAL, "boxcar_search: cell %d is not a power of two in [16, %d]", cell, kBsTile);
+    if (check_cell("boxcar_search", cell, kBsTile)) return PSS_EINVAL;
     const int64_t nq = (T - 1) / cell + 1;
     if (out_ld < nq) return fail(PSS_EINVAL, "boxcar_search: out_ld %lld < %lld cells", (long long)out_ld,
                                  (long long)nq);
     const int64_t ntiles = (T - 1) / kBsTile + 1;
-    if (ntiles > (int64_t)0x7fffffff / ndm)
-        return fail(PSS_EINVAL, "boxcar_search: %lld time tiles x %d trials exceed 2^31 - 1 workgroups",
-                    (long long)ntiles, ndm);
+    const dim3 grid = grid_1d("boxcar_search", ntiles, "time tiles", ndm, "trials");
+    if (!grid.x) return PSS_EINVAL;
     BoxArgs a;
     a.T = T; a.ld = ld; a.out_ld = out_ld; a.nq = nq; a.ntiles = ntiles;
     a.ndm = ndm; a.nw = nw; a.cell = cell;
-    a.lcell = 0;
-    while ((1 << a.lcell) < cell) ++a.lcell;
+    a.lcell = cell_log2(cell);
     hipStream_t st = (hipStream_t)stream;
     switch (nw) {
-        case 13: return bs_launch<16>(plane, mean, rstd, snr, code, a, st);
-        case 12: return bs_launch<8>(plane, mean, rstd, snr, code, a, st);
-        case 11: return bs_launch<4>(plane, mean, rstd, snr, code, a, st);
-        case 10: return bs_launch<2>(plane, mean, rstd, snr, code, a, st);
-        default: return bs_launch<1>(plane, mean, rstd, snr, code, a, st);
+        case 13: return bs_launch<16>(plane, mean, rstd, snr, code, a, grid, st);
+        case 12: return bs_launch<8>(plane, mean, rstd, snr, code, a, grid, st);
+        case 11: return bs_launch<4>(plane, mean, rstd, snr, code, a, grid, st);
+        case 10: return bs_launch<2>(plane, mean, rstd, snr, code, a, grid, st);
+        default: return bs_launch<1>(plane, mean, rstd, snr, code, a, grid, st);
     }
 }
 

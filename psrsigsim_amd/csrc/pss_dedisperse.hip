@@ -14,8 +14,8 @@
 //       trials (wave-uniform, scalar loads of the table):
 //         staged  (dmax - dmin <= kSpread = 2044): the window
 //                 data[c][ws .. t0 + dmax + 2048), ws = (t0 + dmin) & ~3, is
-//                 copied to LDS once (16-B loads when the row is on the 16-B
-//                 grid, VEC, all issued before the first LDS store; dwords
+//                 copied to LDS once (stage_window, pss_window.hpp: 16-B
+//                 loads when the row is on the 16-B grid, VEC; dwords
 //                 otherwise -- the same values) and every
 //                 trial reads its 8 samples per lane from it at the uniform
 //                 offset t0 + d - ws: consecutive lanes read consecutive
@@ -35,6 +35,7 @@
 //       dealt to the XCDs in contiguous runs: the groups of one time tile run
 //       together on one XCD and share its rows in that L2.
 #include "pss_common.hpp"
+#include "pss_window.hpp"
 
 using namespace pss;
 
@@ -53,43 +54,6 @@ struct DdArgs {
     int64_t n, ld, out_ld, T;
     int32_t nchan, ndm, max_delay, ngroups;
 };
-
-// row[ws .. ws + need) -> w[0 .. need), ws % 4 == 0, whole 16-B groups; samples
-// at or past n (never needed) are zeros
-template <bool VEC>
-__device__ __forceinline__ void dd_stage(float *w, const float *row, int64_t ws, int need, int64_t n, int tid) {
-    PSS_DASSERT(need >= 1 && need <= kWin && ws >= 0 && ws + need <= n);
-    const int nq = (need + 3) >> 2;                     // 16-B groups, <= kWin / 4
-    if (VEC && ws + 4 * (int64_t)nq <= n) {
-        // every group inside the row (all but a row's last tile): the loads of
-        // all passes are issued, unconditionally, before the first LDS store
-        // waits for one -- a load-store loop pays one global latency per pass.
-        // The lanes past the last group re-load it (in bounds, one cache line
-        // for all of them); a pass with work stores every lane's value, the
-        // copies in slots of the window that no stored sum reads.
-        constexpr int NP = kWin / 4 / kDdThreads;
-        const float4 *src = reinterpret_cast<const float4 *>(row + ws);
-        float4 v[NP];
-#pragma unroll
-        for (int i = 0; i < NP; ++i) v[i] = src[min(tid + i * kDdThreads, nq - 1)];
-        // (pinned here, or each load sinks into the branch of its store)
-#pragma unroll
-        for (int i = 0; i < NP; ++i) asm volatile("" : "+v"(v[i].x), "+v"(v[i].y), "+v"(v[i].z), "+v"(v[i].w));
-#pragma unroll
-        for (int i = 0; i < NP; ++i)
-            if (i * kDdThreads < nq) *reinterpret_cast<float4 *>(w + 4 * (tid + i * kDdThreads)) = v[i];
-        return;
-    }
-    for (int q = tid; q < nq; q += kDdThreads) {
-        const int64_t s = ws + 4 * q;
-        float4 v;
-        v.x = s < n ? row[s] : 0.0f;
-        v.y = s + 1 < n ? row[s + 1] : 0.0f;
-        v.z = s + 2 < n ? row[s + 2] : 0.0f;
-        v.w = s + 3 < n ? row[s + 3] : 0.0f;
-        *reinterpret_cast<float4 *>(w + 4 * q) = v;
-    }
-}
 
 // acc[i][k] += w[off[i] + tid + 256 k] for NJ trials: off <= kWin - kTB, so the
 // reads stay inside the window whatever the tile's length (a short tile's lanes
@@ -126,9 +90,9 @@ __global__ __launch_bounds__(kDdThreads) void k_dedisperse(const float *__restri
     // Workgroup id -> (time tile, trial group), groups fastest, through the XCD
     // run map: the trial groups of one time tile then run on one XCD, side by
     // side, and its L2 fetches each row once for all of them.
-    const unsigned lid = xcd_run_id();
-    const int g = (int)(lid % (unsigned)a.ngroups);
-    const int64_t t0 = (int64_t)(lid / (unsigned)a.ngroups) * kTB;
+    const uint2 id = xcd_run_pair((unsigned)a.ngroups);
+    const int g = (int)id.y;
+    const int64_t t0 = (int64_t)id.x * kTB;
     const int j0 = g * kND;
     const int nd = min(kND, a.ndm - j0);                       // trials of this group (>= 1)
     const int len = (int)min((int64_t)kTB, a.T - t0);          // times of this tile (>= 1)
@@ -162,7 +126,8 @@ __global__ __launch_bounds__(kDdThreads) void k_dedisperse(const float *__restri
             ws[cb] = (t0 + dmin) & ~(int64_t)3;
             // the window's last needed sample is t0 + len - 1 + dmax <= n - 1
             const int need = (int)(t0 + dmax - ws[cb]) + len;  // <= 3 + kSpread + kTB < kWin
-            dd_stage<VEC>(win[cb], data + (int64_t)c * a.ld, ws[cb], need, a.n, tid);
+            // (samples at or past n, never needed, are zeros; ws >= 0: no HEAD)
+            stage_window<kDdThreads, kWin, VEC, false>(win[cb], data + (int64_t)c * a.ld, ws[cb], need, a.n, tid);
         }
         __syncthreads();
 #pragma unroll
@@ -220,13 +185,11 @@ int pss_dedisperse(const float *data, int32_t nchan, int64_t n, int64_t ld, cons
                                 (long long)T);
     const int64_t ngroups = ((int64_t)ndm + kND - 1) / kND;
     const int64_t ntiles = (T + kTB - 1) / kTB;
-    if (ntiles > (int64_t)0x7fffffff / ngroups)
-        return fail(PSS_EINVAL, "dedisperse: %lld time tiles x %lld trial groups exceed 2^31 - 1 workgroups",
-                    (long long)ntiles, (long long)ngroups);
+    const dim3 grid = grid_1d("dedisperse", ntiles, "time tiles", ngroups, "trial groups");
+    if (!grid.x) return PSS_EINVAL;
     DdArgs a;
     a.n = n; a.ld = ld; a.nchan = nchan; a.ndm = ndm; a.max_delay = max_delay;
     a.ngroups = (int32_t)ngroups; a.out_ld = out_ld; a.T = T;
-    const dim3 grid((unsigned)(ntiles * ngroups));
     // 16-B loads of the staged windows need the rows on the 16-B grid.  Same bits.
     if (on_grid16(data, ld))
         k_dedisperse<true><<<grid, dim3(kDdThreads), 0, (hipStream_t)stream>>>(data, delays, out, a);

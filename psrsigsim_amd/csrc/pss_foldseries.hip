@@ -254,9 +254,9 @@ __global__ __launch_bounds__(kFsThreads) void k_fold_series(const float *__restr
     PSS_DASSERT(nbin >= 2 && nbin <= (uint32_t)(NS * kFsThreads) && (NS == 1 || nbin > (uint32_t)(NS / 2 * kFsThreads)));
 
     // workgroup id -> (row, sub-integration), sub-integrations fastest, through the XCD run map
-    const unsigned lid = xcd_run_id();
-    const int r = (int)(lid / (unsigned)a.nsub);
-    const int s = (int)(lid % (unsigned)a.nsub);
+    const uint2 id = xcd_run_pair((unsigned)a.nsub);
+    const int r = (int)id.x;
+    const int s = (int)id.y;
     PSS_DASSERT(r >= 0 && r < a.nrows);
     const int ser = min(max(src[r], 0), a.nser - 1);
     const uint64_t inc = min(inc_t[r], a.inc_max);
@@ -335,15 +335,14 @@ int pss_fold_series(const float *x, int32_t nser, int64_t T, int64_t ld, const i
         return fail(PSS_EINVAL, "fold_series: nsub %d x L %lld > T %lld", nsub, (long long)L, (long long)T);
     if (ld < T) return fail(PSS_EINVAL, "fold_series: ld %lld < T %lld", (long long)ld, (long long)T);
     if (nbin < 2 || nbin > kFsMaxBin) return fail(PSS_EINVAL, "fold_series: nbin %d outside [2, %d]", nbin, kFsMaxBin);
-    if ((int64_t)nrows > (int64_t)0x7fffffff / nsub)
-        return fail(PSS_EINVAL, "fold_series: %d rows x %d sub-integrations exceed 2^31 - 1 workgroups", nrows, nsub);
+    const dim3 grid = grid_1d("fold_series", nrows, "rows", nsub, "sub-integrations");
+    if (!grid.x) return PSS_EINVAL;
     FoldArgs a;
     a.T = T; a.ld = ld; a.L = L;
     a.nser = nser; a.nrows = nrows; a.nsub = nsub; a.nbin = nbin;
     // floor(2^64 / nbin) from 2^64 - 1 = q nbin + rem
     a.inc_max = ~(uint64_t)0 / (uint64_t)nbin + (~(uint64_t)0 % (uint64_t)nbin == (uint64_t)nbin - 1 ? 1 : 0);
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)((int64_t)nrows * nsub));
     if (nbin <= kFsThreads)
         k_fold_series<1><<<grid, dim3(kFsThreads), 0, st>>>(x, src, inc, phi0, out, hits, a);
     else if (nbin <= 2 * kFsThreads)

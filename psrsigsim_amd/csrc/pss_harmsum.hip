@@ -86,9 +86,9 @@ template <int SRC>
 __global__ __launch_bounds__(kHsThreads) void k_hs_power(const float *__restrict__ spec,
                                                          const float *__restrict__ scale, float *__restrict__ work,
                                                          HarmArgs a) {
-    const unsigned lid = xcd_run_id();                     // (trial, tile) as k_harmonic_search
-    const int j = (int)(lid / (unsigned)a.ntiles);
-    const int k0 = (int)(lid % (unsigned)a.ntiles) * kHsTile;
+    const uint2 id = xcd_run_pair((unsigned)a.ntiles);     // (trial, tile) as k_harmonic_search
+    const int j = (int)id.x;
+    const int k0 = (int)id.y * kHsTile;
     PSS_DASSERT(j >= 0 && j < a.ndm && k0 < a.nbin);
     const float sc = scale[j];
     const float *row = spec + 2 * ((int64_t)j * a.ld);
@@ -114,9 +114,9 @@ __global__ __launch_bounds__(kHsThreads) void k_harmonic_search(const float *__r
     PSS_DASSERT(a.nl >= 1 && a.nl <= kHsMaxL && a.kmin >= 1 && a.nbin <= kHsMaxBin);
 
     // workgroup id -> (trial, tile), tiles fastest, through the XCD run map
-    const unsigned lid = xcd_run_id();
-    const int j = (int)(lid / (unsigned)a.ntiles);
-    const int k0 = (int)(lid % (unsigned)a.ntiles) * kHsTile;
+    const uint2 id = xcd_run_pair((unsigned)a.ntiles);
+    const int j = (int)id.x;
+    const int k0 = (int)id.y * kHsTile;
     PSS_DASSERT(j >= 0 && j < a.ndm && k0 < a.nbin);
     const float sc = scale[j];
     // (SRC = kHsPow: spec is the workspace, rows of nbin powers)
@@ -196,22 +196,18 @@ int pss_harmonic_search(const float *spec, int32_t ndm, int64_t nbin, int64_t ld
     if (ld < nbin) return fail(PSS_EINVAL, "harmonic_search: ld %lld < nbin %lld", (long long)ld, (long long)nbin);
     if (nl < 1 || nl > kHsMaxL) return fail(PSS_EINVAL, "harmonic_search: nl %d outside [1, %d]", nl, kHsMaxL);
     if (kmin < 1) return fail(PSS_EINVAL, "harmonic_search: kmin %lld < 1", (long long)kmin);
-    if (cell < 16 || cell > kHsTile || (cell & (cell - 1)))
-        return fail(PSS_EINVAL, "harmonic_search: cell %d is not a power of two in [16, %d]", cell, kHsTile);
+    if (check_cell("harmonic_search", cell, kHsTile)) return PSS_EINVAL;
     const int64_t nq = (nbin - 1) / cell + 1;
     if (out_ld < nq) return fail(PSS_EINVAL, "harmonic_search: out_ld %lld < %lld cells", (long long)out_ld,
                                  (long long)nq);
     const int64_t ntiles = (nbin - 1) / kHsTile + 1;
-    if (ntiles > (int64_t)0x7fffffff / ndm)
-        return fail(PSS_EINVAL, "harmonic_search: %lld bin tiles x %d trials exceed 2^31 - 1 workgroups",
-                    (long long)ntiles, ndm);
+    const dim3 grid = grid_1d("harmonic_search", ntiles, "bin tiles", ndm, "trials");
+    if (!grid.x) return PSS_EINVAL;
     HarmArgs a;
     a.nbin = nbin; a.ld = ld; a.out_ld = out_ld; a.nq = nq; a.ntiles = ntiles; a.kmin = kmin;
     a.ndm = ndm; a.nl = nl; a.cell = cell;
-    a.lcell = 0;
-    while ((1 << a.lcell) < cell) ++a.lcell;
+    a.lcell = cell_log2(cell);
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)(ntiles * ndm));
     // 8-B loads of a complex element need the rows on the 8-B grid (a float pointer
     // promises 4).  Same bits.
     const bool vec = (uintptr_t)spec % 8 == 0;

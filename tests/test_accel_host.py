@@ -4,7 +4,6 @@ argument checks, which precede any launch, the properties of the definition
 (tests/accel_ref.py) that the kernel's bounds rest on, and the CPU study that
 motivates the stage: an accelerated pulse train is found at its own trial
 acceleration and lost at zero."""
-import ctypes
 import os
 import re
 from fractions import Fraction
@@ -15,6 +14,7 @@ import pytest
 from psrsigsim_amd import _lib
 from tests import accel_ref as ref
 from tests import periodicity_ref as pref
+from tests.kernel_harness import check_rejections, host_pointer
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 C = 299792458.0
@@ -137,25 +137,18 @@ def test_entry_point_is_declared_exported_and_hashed():
 def test_entry_point_validates_arguments():
     """Every PSS_EINVAL of pss_accel_resample with NULL or host pointers: the
     checks precede any launch (no GPU touched)."""
-    L = _lib.load()
-    host = (ctypes.c_float * 64)()
-    p = ctypes.cast(host, ctypes.c_void_p)
-
-    def call(x=p, nser=2, T=16, ld=16, src=p, kappa=p, sub=None, nrows=3, n_out=16, out=p, out_ld=16):
-        return L.pss_accel_resample(x, nser, T, ld, src, kappa, sub, nrows, n_out, out, out_ld, None)
-
+    p = host_pointer()
+    good = dict(x=p, nser=2, T=16, ld=16, src=p, kappa=p, sub=None, nrows=3, n_out=16, out=p, out_ld=16)
     big = (1 << 31) - 1
-    for kw, msg in ((dict(x=None), "x is NULL"), (dict(src=None), "src is NULL"), (dict(kappa=None), "kappa is NULL"),
+    check_rejections(_lib.load().pss_accel_resample, good,
+                   ((dict(x=None), "x is NULL"), (dict(src=None), "src is NULL"), (dict(kappa=None), "kappa is NULL"),
                     (dict(out=None), "out is NULL"), (dict(nser=0), "nser 0 < 1"), (dict(nrows=0), "nrows 0 < 1"),
                     (dict(nrows=-2), "nrows -2 < 1"), (dict(T=0, ld=0), "T 0 < 1"),
                     (dict(T=1 << 31, ld=1 << 31), "T 2147483648 > 2^31 - 1"), (dict(ld=15), "ld 15 < T 16"),
                     (dict(n_out=0), "n_out 0 < 1"), (dict(n_out=17, out_ld=17), "n_out 17 > T 16"),
                     (dict(out_ld=15), "out_ld 15 < n_out 16"),
                     (dict(T=big, ld=big, n_out=big, out_ld=big, nrows=1 << 14),
-                     "1048576 time tiles x 2048 row groups exceed 2^31 - 1 workgroups")):
-        assert call(**kw) == _lib.PSS_EINVAL, kw
-        assert msg in _lib.last_error(), (kw, _lib.last_error())
-        assert _lib.last_error().startswith("accel_resample: "), _lib.last_error()
+                     "1048576 time tiles x 2048 row groups exceed 2^31 - 1 workgroups")), prefix="accel_resample: ")
 
 
 # ---------------------------------------------------------------------------

@@ -2,18 +2,16 @@
 the prototype filter, every Python-level and C-ABI rejection (nothing reaches
 the device), and the host-planned noise scale against the value recorded from
 the reference's ``Receiver._make_amp_noise`` (tests/golden/make_bb_noise.py)."""
-import ctypes
-
 import numpy as np
 import pytest
 
 from psrsigsim_amd import _lib
 from tests.fixtures_util import load
+from tests.kernel_harness import backend, check_rejections, host_pointer
 
 
 def _backend():
-    from psrsigsim_amd.telescope import Backend
-    return Backend(samprate=1.0, name="B")
+    return backend(samprate=1.0)
 
 
 @pytest.mark.parametrize("C,T", [(16, 1), (64, 1), (16, 2), (64, 4), (512, 8), (4096, 3)])
@@ -100,38 +98,29 @@ def test_cabi_rejections():
     """NULL pointers, ld < n, out_ld < S and the parameter ranges return
     PSS_EINVAL with no device touched; S = 0 returns PSS_OK without a launch."""
     L = _lib.load()
-    host = (ctypes.c_float * 64)()
-    p = ctypes.cast(host, ctypes.c_void_p)
-    E, OK = _lib.PSS_EINVAL, _lib.PSS_OK
+    p = host_pointer()
+    OK = _lib.PSS_OK
     # pss_channelize(x, npol, n, ld, h, nchan, ntap, tscrunch, out, out_ld, stream)
-    assert L.pss_channelize(None, 2, 640, 640, p, 16, 1, 1, p, 20, None) == E
-    assert L.pss_channelize(p, 2, 640, 640, None, 16, 1, 1, p, 20, None) == E
-    assert L.pss_channelize(p, 2, 640, 640, p, 16, 1, 1, None, 20, None) == E
-    assert L.pss_channelize(p, 2, 640, 639, p, 16, 1, 1, p, 20, None) == E               # ld < n
-    assert "ld 639" in _lib.last_error()
-    assert L.pss_channelize(p, 2, 640, 640, p, 16, 1, 1, p, 19, None) == E               # out_ld < S = 20
-    assert "out_ld 19" in _lib.last_error()
-    assert L.pss_channelize(p, 2, 640, 640, p, 16, 4, 3, p, 4, None) == E                # S = (20 - 3) // 3 = 5
-    for npol in (0, 3, -1):
-        assert L.pss_channelize(p, npol, 640, 640, p, 16, 1, 1, p, 20, None) == E
-    for C in (8, 0, -16, 24, 8192):
-        assert L.pss_channelize(p, 2, 1 << 20, 1 << 20, p, C, 1, 1, p, 1 << 20, None) == E
-    assert "nchan" in _lib.last_error()
-    for T in (0, 9, -2):
-        assert L.pss_channelize(p, 2, 640, 640, p, 16, T, 1, p, 20, None) == E
-    assert L.pss_channelize(p, 2, 640, 640, p, 16, 1, 0, p, 20, None) == E               # tscrunch < 1
-    assert L.pss_channelize(p, 2, -1, 640, p, 16, 1, 1, p, 20, None) == E
+    good = dict(x=p, npol=2, n=640, ld=640, h=p, nchan=16, ntap=1, tscrunch=1, out=p, out_ld=20)
+    big = dict(n=1 << 20, ld=1 << 20, out_ld=1 << 20)
+    check_rejections(L.pss_channelize, good,
+                     [(dict(x=None), ""), (dict(h=None), ""), (dict(out=None), ""),
+                      (dict(ld=639), "ld 639"),                                          # ld < n
+                      (dict(out_ld=19), "out_ld 19"),                                    # out_ld < S = 20
+                      (dict(ntap=4, tscrunch=3, out_ld=4), "")] +                        # S = (20 - 3) // 3 = 5
+                     [(dict(npol=npol), "") for npol in (0, 3, -1)] +
+                     [(dict(big, nchan=C), "") for C in (8, 0, -16, 24)] + [(dict(big, nchan=8192), "nchan")] +
+                     [(dict(ntap=T), "") for T in (0, 9, -2)] +
+                     [(dict(tscrunch=0), ""), (dict(n=-1), "")])
     # nothing to do: no whole frame, fewer frames than taps, no whole scrunch group
     assert L.pss_channelize(p, 2, 31, 31, p, 16, 1, 1, p, 0, None) == OK
     assert L.pss_channelize(p, 1, 32 * 7, 32 * 7, p, 16, 8, 1, p, 0, None) == OK
     assert L.pss_channelize(p, 2, 32 * 5, 32 * 5, p, 16, 1, 6, p, 0, None) == OK
     assert L.pss_channelize(p, 2, 0, 0, p, 4096, 1, 1, p, 0, None) == OK
     # pss_normal_add(rows, nrows, n, ld, scale, seed, call_id, stream)
-    assert L.pss_normal_add(None, 2, 100, 100, 1.0, 1, 1, None) == E
-    assert L.pss_normal_add(p, 2, 100, 99, 1.0, 1, 1, None) == E                         # ld < n
-    assert "ld 99" in _lib.last_error()
-    assert L.pss_normal_add(p, 65536, 100, 100, 1.0, 1, 1, None) == E
-    assert L.pss_normal_add(p, 2, -1, 100, 1.0, 1, 1, None) == E
+    good = dict(rows=p, nrows=2, n=100, ld=100, scale=1.0, seed=1, call_id=1)
+    check_rejections(L.pss_normal_add, good, ((dict(rows=None), ""), (dict(ld=99), "ld 99"),          # ld < n
+                                              (dict(nrows=65536), ""), (dict(n=-1), "")))
     assert L.pss_normal_add(p, 0, 100, 100, 1.0, 1, 1, None) == OK                        # no rows
     assert L.pss_normal_add(p, 2, 0, 100, 1.0, 1, 1, None) == OK                          # no samples
 

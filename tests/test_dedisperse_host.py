@@ -2,19 +2,13 @@
 against an independent float64 restatement, a sharded signal's columns, every
 Python-level rejection (nothing reaches the device) and the C ABI's argument
 checks, which precede any launch."""
-import ctypes
-
 import numpy as np
 import pytest
 
 from psrsigsim_amd import _lib
+from tests.kernel_harness import backend as _backend, check_rejections, host_pointer
 
 DMS = np.arange(0, 65, 5)
-
-
-def _backend():
-    from psrsigsim_amd.telescope import Backend
-    return Backend(samprate=0.01, name="B")
 
 
 class _StubBuf(object):
@@ -126,19 +120,11 @@ def test_rejections_never_reach_the_device(monkeypatch):
 def test_cabi_rejections():
     """NULL pointers and each out-of-range scalar return PSS_EINVAL with the
     argument named and no device touched."""
-    L = _lib.load()
-    host = (ctypes.c_float * 64)()
-    p = ctypes.cast(host, ctypes.c_void_p)
-    E = _lib.PSS_EINVAL
+    p = host_pointer()
     # pss_dedisperse(data, nchan, n, ld, delays, ndm, max_delay, out, out_ld, stream)
     good = dict(data=p, nchan=4, n=100, ld=100, delays=p, ndm=3, max_delay=10, out=p, out_ld=90)
-
-    def call(**kw):
-        a = dict(good, **kw)
-        return L.pss_dedisperse(a["data"], a["nchan"], a["n"], a["ld"], a["delays"], a["ndm"], a["max_delay"],
-                                a["out"], a["out_ld"], None)
-
-    for kw, word in ((dict(data=None), "data"), (dict(delays=None), "delays"), (dict(out=None), "out"),
+    check_rejections(_lib.load().pss_dedisperse, good,
+                    ((dict(data=None), "data"), (dict(delays=None), "delays"), (dict(out=None), "out"),
                      (dict(nchan=0), "nchan 0"), (dict(nchan=-3), "nchan -3"),
                      (dict(ndm=0), "ndm 0"), (dict(ndm=-1), "ndm -1"),
                      (dict(ld=99), "ld 99"),
@@ -147,6 +133,4 @@ def test_cabi_rejections():
                      (dict(n=0, ld=0, max_delay=0), "max_delay 0 >= n 0"),
                      (dict(out_ld=89), "out_ld 89"), (dict(max_delay=0, out_ld=99), "out_ld 99"),
                      # the launch grid: ceil(T / 2048) * ceil(ndm / 8) workgroups in 31 bits
-                     (dict(n=1 << 40, ld=1 << 40, out_ld=1 << 40, ndm=64), "workgroups")):
-        assert call(**kw) == E, kw
-        assert word in _lib.last_error(), (kw, _lib.last_error())
+                     (dict(n=1 << 40, ld=1 << 40, out_ld=1 << 40, ndm=64), "workgroups")))

@@ -3,7 +3,6 @@ Python-level rejection of ``Backend._fold_plan`` (nothing reaches the device),
 its DM bookkeeping and chunking, the C ABI's argument checks, which precede
 any launch, and ``FoldedCandidates.refine`` on cubes built in NumPy against
 the plain-loop restatement (tests/fold_ref.py)."""
-import ctypes
 import os
 import re
 
@@ -12,6 +11,7 @@ import pytest
 
 from psrsigsim_amd import _lib
 from tests import fold_ref as ref
+from tests.kernel_harness import check_rejections, host_pointer
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -205,23 +205,17 @@ def test_entry_point_is_declared_exported_and_hashed():
 def test_entry_point_validates_arguments():
     """Every PSS_EINVAL of pss_fold_series with NULL or host pointers: the
     checks precede any launch (no GPU touched)."""
-    L = _lib.load()
-    host = (ctypes.c_float * 64)()
-    p = ctypes.cast(host, ctypes.c_void_p)
-
-    def call(x=p, nser=2, T=16, ld=16, src=p, inc=p, phi0=None, nrows=3, nsub=2, Ls=8, nbin=4, out=p, hits=None):
-        return L.pss_fold_series(x, nser, T, ld, src, inc, phi0, nrows, nsub, Ls, nbin, out, hits, None)
-
-    for kw, msg in ((dict(x=None), "x is NULL"), (dict(src=None), "src is NULL"), (dict(inc=None), "inc is NULL"),
+    p = host_pointer()
+    good = dict(x=p, nser=2, T=16, ld=16, src=p, inc=p, phi0=None, nrows=3, nsub=2, Ls=8, nbin=4, out=p, hits=None)
+    check_rejections(_lib.load().pss_fold_series, good,
+                   ((dict(x=None), "x is NULL"), (dict(src=None), "src is NULL"), (dict(inc=None), "inc is NULL"),
                     (dict(out=None), "out is NULL"), (dict(nser=0), "nser 0 < 1"), (dict(nrows=0), "nrows 0 < 1"),
                     (dict(nrows=-2), "nrows -2 < 1"), (dict(nsub=0), "nsub 0 < 1"), (dict(Ls=0), "L 0 < 1"),
                     (dict(Ls=9), "nsub 2 x L 9 > T 16"), (dict(nsub=3, Ls=6), "nsub 3 x L 6 > T 16"),
                     (dict(Ls=1 << 62, nsub=4), "x L 4611686018427387904 > T 16"),
                     (dict(ld=15), "ld 15 < T 16"), (dict(nbin=1), "nbin 1 outside [2, 1024]"),
                     (dict(nbin=1025), "nbin 1025 outside [2, 1024]"), (dict(nbin=0), "nbin 0 outside"),
-                    (dict(nrows=1 << 30, nsub=2), "exceed 2^31 - 1 workgroups")):
-        assert call(**kw) == _lib.PSS_EINVAL, kw
-        assert msg in _lib.last_error(), (kw, _lib.last_error())
+                    (dict(nrows=1 << 30, nsub=2), "exceed 2^31 - 1 workgroups")))
 
 
 # ---------------------------------------------------------------------------

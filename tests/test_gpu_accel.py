@@ -23,6 +23,8 @@ import numpy as np
 import pytest
 
 from tests import accel_ref as ref
+from tests import kernel_harness as kh
+from tests.kernel_harness import same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -31,10 +33,6 @@ IN_GUARD = float(1 << 20)
 OUT_GUARD = -7.0
 GUARD_ROWS = 2
 I64_MIN, I64_MAX = -(1 << 63), (1 << 63) - 1
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
 def data(nser, T, seed):
@@ -90,26 +88,19 @@ def _case(name):
     raise KeyError(name)
 
 
-_REF = {}
-
-
+@kh.once
 def reference(name):
     """A case and its oracle, computed once and shared (read-only)."""
-    if name not in _REF:
-        x, src, kap, sub, n_out = _case(name)
-        want = ref.resample(x, src, kap, sub, n_out)
-        for a in (x, want):
-            a.setflags(write=False)
-        _REF[name] = (x, src, kap, sub, n_out, want)
-    return _REF[name]
+    x, src, kap, sub, n_out = _case(name)
+    return x, src, kap, sub, n_out, ref.resample(x, src, kap, sub, n_out)
 
 
 def run_kernel(hip_lib, x, src, kappa, sub, n_out, ld=None, out_ld=None, in_off=0, out_off=0, want_ptr=False):
-    """pss_accel_resample on views inside larger tensors.  ``x`` sits at float
-    offset 8192 + GUARD_ROWS * ld + in_off of its parent (row stride ld),
-    ``out`` at 64 + out_off (row stride out_ld); the rest of both parents are
-    guards.  Returns out [nrows][n_out] after checking that nothing outside
-    out[r][0 .. n_out) was written."""
+    """pss_accel_resample on views inside larger tensors (tests/kernel_harness.py):
+    ``x`` with row stride ld between guards that include GUARD_ROWS whole rows
+    on either side, ``out`` with row stride out_ld.  Returns out
+    [nrows][n_out] after checking that nothing outside out[r][0 .. n_out) was
+    written."""
     import torch
     from psrsigsim_amd import _lib
     nser, T = x.shape
@@ -117,28 +108,18 @@ def run_kernel(hip_lib, x, src, kappa, sub, n_out, ld=None, out_ld=None, in_off=
     ld = T + 5 if ld is None else ld
     out_ld = (n_out + 7) // 4 * 4 if out_ld is None else out_ld
     assert ld > T and out_ld > n_out
-    lead = 8192 + GUARD_ROWS * ld + in_off
-    parent = torch.full((lead + (nser + GUARD_ROWS) * ld + 8192,), IN_GUARD, dtype=torch.float32, device="cuda")
-    view = parent[lead:lead + nser * ld].view(nser, ld)
-    view[:, :T] = torch.from_numpy(np.array(x, dtype=np.float32)).cuda()
-    olead = 64 + out_off
-    oparent = torch.full((olead + nrows * out_ld + 64,), OUT_GUARD, dtype=torch.float32, device="cuda")
-    oview = oparent[olead:olead + nrows * out_ld].view(nrows, out_ld)
+    xin = kh.GuardedInput(x, ld, in_off, IN_GUARD, guard_rows=GUARD_ROWS)
+    out = kh.GuardedOutput(nrows, n_out, out_ld, out_off, OUT_GUARD)
     src_d = torch.from_numpy(np.array(src, dtype=np.int32)).cuda()
     kap_d = torch.from_numpy(np.array(kappa, dtype=np.int64)).cuda()
     sub_d = None if sub is None else torch.from_numpy(np.array(sub, dtype=np.float32)).cuda()
     torch.cuda.synchronize()
-    rc = hip_lib.pss_accel_resample(view.data_ptr(), nser, T, ld, src_d.data_ptr(), kap_d.data_ptr(),
-                                    None if sub_d is None else sub_d.data_ptr(), nrows, n_out, oview.data_ptr(),
-                                    out_ld, None)
+    rc = hip_lib.pss_accel_resample(xin.ptr, nser, T, ld, src_d.data_ptr(), kap_d.data_ptr(),
+                                    None if sub_d is None else sub_d.data_ptr(), nrows, n_out, out.ptr, out_ld, None)
     _lib.check(rc, "accel_resample")
     torch.cuda.synchronize()
-    o = oparent.cpu().numpy()
-    body = o[olead:olead + nrows * out_ld].reshape(nrows, out_ld)
-    assert np.all(o[:olead] == OUT_GUARD) and np.all(o[olead + nrows * out_ld:] == OUT_GUARD)
-    assert np.all(body[:, n_out:] == OUT_GUARD)
-    got = np.ascontiguousarray(body[:, :n_out])
-    return (got, view.data_ptr()) if want_ptr else got
+    got = out.read()
+    return (got, xin.ptr) if want_ptr else got
 
 
 def routes(ptr, ld, nser, T, n_out, src, kappa):
@@ -254,11 +235,6 @@ def test_rows_are_independent(hip_lib):
 # ---------------------------------------------------------------------------
 # the API
 # ---------------------------------------------------------------------------
-def _backend():
-    from psrsigsim_amd.telescope import Backend
-    return Backend(samprate=0.01, name="B")
-
-
 def _plane(x, samprate=0.01):
     import torch
     from psrsigsim_amd.telescope import DedispersedPlane
@@ -280,7 +256,7 @@ def _series(T):
 def test_api_resample(hip_lib):
     import torch
     from psrsigsim_amd.telescope import Backend
-    be = _backend()
+    be = kh.backend()
     T = 4500
     x, mean, sigma = _series(T)
     plane = _plane(x)
@@ -310,7 +286,7 @@ def test_api_snr_at_zero_is_the_periodicity_search(hip_lib, T):
     measured statistics (4374 = 2 x 3^7 is a transform length off the 16-B
     grid)."""
     import torch
-    be = _backend()
+    be = kh.backend()
     x, mean, sigma = _series(T)
     plane = _plane(x)
     for kw in (dict(mean=mean, std=sigma, nharm=8, cell=64, fmin=3.0), dict(), dict(nharm=2, nfft=2 * T)):
@@ -330,7 +306,7 @@ def test_api_snr_chunking_and_ties(hip_lib):
     acceleration given first."""
     import torch
     from psrsigsim_amd.telescope import Backend
-    be = _backend()
+    be = kh.backend()
     T = 4500
     x, mean, sigma = _series(T)
     plane = _plane(x)

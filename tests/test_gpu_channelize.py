@@ -30,6 +30,9 @@ statistics and search-mode PSRFITS output of the channelised signal follow.
 import numpy as np
 import pytest
 
+from tests import kernel_harness as kh
+from tests.kernel_harness import engine_seed_restored  # noqa: F401 (autouse here)
+
 pytestmark = pytest.mark.gpu
 
 C_POCKETFFT = 0.178
@@ -113,25 +116,17 @@ def pocketfft_constant():
     return worst
 
 
-_REF = {}
-
-
+@kh.once
 def reference(case):
     """The float64 reference of a case, computed once and shared."""
-    if case not in _REF:
-        C, T, ts, npol, M = case
-        x = make_input(case)
-        ref, E = ref_channelize(x, C, T, ts)
-        ref.setflags(write=False)
-        E.setflags(write=False)
-        x.setflags(write=False)
-        _REF[case] = (x, ref, E)
-    return _REF[case]
+    C, T, ts, npol, M = case
+    x = make_input(case)
+    return (x,) + ref_channelize(x, C, T, ts)
 
 
 def run_kernel(hip_lib, x, C, T, ts, ld=None, out_ld=None, fill=-7.0):
-    """pss_channelize on host array x [npol][N]; returns (out [C][S], pad
-    columns [C][out_ld - S])."""
+    """pss_channelize on host array x [npol][N] (guarded views,
+    tests/kernel_harness.py); returns (out [C][S], pad columns [C][out_ld - S])."""
     import torch
     from psrsigsim_amd import _lib
     npol, N = x.shape
@@ -139,16 +134,13 @@ def run_kernel(hip_lib, x, C, T, ts, ld=None, out_ld=None, fill=-7.0):
     S = (N // L - T + 1) // ts
     ld = N if ld is None else ld
     out_ld = S if out_ld is None else out_ld
-    xd = torch.zeros((npol, ld), dtype=torch.float32, device="cuda")
-    xd[:, :N] = torch.from_numpy(np.array(x, dtype=np.float32))
-    xd[:, N:] = float("nan")                      # (read past n would poison the output)
+    xd = kh.GuardedInput(x, ld, guard=float("nan"))           # (a read past n would poison the output)
     h = torch.from_numpy(pfb(C, T).astype(np.float32)).cuda()
-    out = torch.full((C, out_ld), fill, dtype=torch.float32, device="cuda")
-    rc = hip_lib.pss_channelize(xd.data_ptr(), npol, N, ld, h.data_ptr(), C, T, ts, out.data_ptr(), out_ld, None)
+    out = kh.GuardedOutput(C, S, out_ld, guard=fill)
+    rc = hip_lib.pss_channelize(xd.ptr, npol, N, ld, h.data_ptr(), C, T, ts, out.ptr, out_ld, None)
     _lib.check(rc, "channelize")
     torch.cuda.synchronize()
-    o = out.cpu().numpy()
-    return o[:, :S], o[:, S:]
+    return out.read(), out.rows_with_pad()[:, S:]
 
 
 @pytest.mark.parametrize("aligned", [True, False], ids=["vec", "elem"])
@@ -266,16 +258,6 @@ BW = 0.512                      # MHz: 1.024 MHz sampling
 PERIOD = 0.016                  # s: 16384 voltage samples, 128 channelised samples at C = 64
 NSAMP = 1 << 21
 TSYS, SMEAN = 100.0, 1e-5       # a noise scale of the order of the pulse amplitudes
-
-
-@pytest.fixture(autouse=True)
-def _engine_seed_restored():
-    """The tests below seed the engine: put its seed and call counter back,
-    pass or fail."""
-    from psrsigsim_amd import _engine
-    saved = dict(_engine._state)
-    yield
-    _engine._state.update(saved)
 
 
 def _make_bb():

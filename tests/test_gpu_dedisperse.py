@@ -23,6 +23,9 @@ goes trial by trial.
 import numpy as np
 import pytest
 
+from tests import kernel_harness as kh
+from tests.kernel_harness import engine_seed_restored  # noqa: F401 (autouse here)
+
 pytestmark = pytest.mark.gpu
 
 TB, ND, SPREAD = 2048, 8, 2044
@@ -103,25 +106,18 @@ def _case(name):
     raise KeyError(name)
 
 
-_REF = {}
-
-
+@kh.once
 def reference(name):
     """A case and its float64 oracle, computed once and shared (read-only)."""
-    if name not in _REF:
-        data, tab, md = _case(name)
-        ref = oracle(data, tab, md)
-        for a in (data, tab, ref):
-            a.setflags(write=False)
-        _REF[name] = (data, tab, md, ref)
-    return _REF[name]
+    data, tab, md = _case(name)
+    return data, tab, md, oracle(data, tab, md)
 
 
 def run_kernel(hip_lib, data, table, max_delay, ld=None, out_ld=None, in_off=0, out_off=0):
-    """pss_dedisperse on views inside larger tensors.  ``data`` sits at float
-    offset 8192 + in_off of its parent (row stride ld), ``out`` at 64 + out_off
-    (row stride out_ld); the rest of both parents are guards.  Returns out
-    [nDM][T] after checking that nothing outside out[j][0 .. T) was written."""
+    """pss_dedisperse on views inside larger tensors (tests/kernel_harness.py):
+    ``data`` with row stride ld between guards, ``out`` with row stride out_ld.
+    Returns out [nDM][T] after checking that nothing outside out[j][0 .. T)
+    was written."""
     import torch
     from psrsigsim_amd import _lib
     C, N = data.shape
@@ -130,23 +126,13 @@ def run_kernel(hip_lib, data, table, max_delay, ld=None, out_ld=None, in_off=0, 
     ld = N + 5 if ld is None else ld
     out_ld = T + 3 if out_ld is None else out_ld
     assert ld > N and out_ld > T
-    lead = 8192 + in_off
-    parent = torch.full((lead + C * ld + 8192,), IN_GUARD, dtype=torch.float32, device="cuda")
-    view = parent[lead:lead + C * ld].view(C, ld)
-    view[:, :N] = torch.from_numpy(np.array(data, dtype=np.float32)).cuda()
-    olead = 64 + out_off
-    oparent = torch.full((olead + ndm * out_ld + 64,), OUT_GUARD, dtype=torch.float32, device="cuda")
-    oview = oparent[olead:olead + ndm * out_ld].view(ndm, out_ld)
+    x = kh.GuardedInput(data, ld, in_off, IN_GUARD)
+    out = kh.GuardedOutput(ndm, T, out_ld, out_off, OUT_GUARD)
     tab = torch.from_numpy(np.array(table, dtype=np.int32)).cuda()
-    rc = hip_lib.pss_dedisperse(view.data_ptr(), C, N, ld, tab.data_ptr(), ndm, max_delay, oview.data_ptr(), out_ld,
-                                None)
+    rc = hip_lib.pss_dedisperse(x.ptr, C, N, ld, tab.data_ptr(), ndm, max_delay, out.ptr, out_ld, None)
     _lib.check(rc, "dedisperse")
     torch.cuda.synchronize()
-    o = oparent.cpu().numpy()
-    assert (o[:olead] == OUT_GUARD).all() and (o[olead + ndm * out_ld:] == OUT_GUARD).all()
-    rows = o[olead:olead + ndm * out_ld].reshape(ndm, out_ld)
-    assert (rows[:, T:] == OUT_GUARD).all()                       # nothing written past T
-    return rows[:, :T].copy()
+    return out.read()
 
 
 KERNEL_CASES = ["copy", "odd", "physical", "growing", "channels", "ragged", "wide", "runs12"]
@@ -174,11 +160,7 @@ def test_misaligned_views_give_the_same_bits(name, hip_lib):
     Na, Ta = (N + 3) // 4 * 4, (T + 3) // 4 * 4
     base = run_kernel(hip_lib, data, tab, md, ld=Na + 4, out_ld=Ta + 4)
     assert np.array_equal(base.astype(np.float64), ref)
-    odd = lambda v: v + 1 - (v % 2)
-    for kw in (dict(ld=odd(N + 2), out_ld=odd(T + 2), in_off=1, out_off=1),      # everything off the grid
-               dict(ld=Na + 4, out_ld=Ta + 4, in_off=1, out_off=0),             # the base alone
-               dict(ld=odd(N + 2), out_ld=Ta + 4, in_off=0, out_off=0),         # the row stride alone
-               dict(ld=Na + 4, out_ld=odd(T + 2), in_off=0, out_off=1)):        # the output alone
+    for kw in kh.misaligned_layouts(Na + 4, Ta + 4, kh.odd(N + 2), kh.odd(T + 2)):
         got = run_kernel(hip_lib, data, tab, md, **kw)
         assert got.tobytes() == base.tobytes(), kw
 
@@ -232,19 +214,6 @@ def test_float_data_within_the_any_order_bound(hip_lib):
 # ---------------------------------------------------------------------------
 # API
 # ---------------------------------------------------------------------------
-@pytest.fixture(autouse=True)
-def _engine_seed_restored():
-    from psrsigsim_amd import _engine
-    saved = dict(_engine._state)
-    yield
-    _engine._state.update(saved)
-
-
-def _backend():
-    from psrsigsim_amd.telescope import Backend
-    return Backend(samprate=0.01, name="B")
-
-
 def test_api_on_a_search_mode_signal(hip_lib):
     import torch
     from psrsigsim_amd.signal import FilterBankSignal
@@ -253,7 +222,7 @@ def test_api_on_a_search_mode_signal(hip_lib):
     sig = FilterBankSignal(1400, 400, Nsubband=64, sample_rate=0.01, fold=False)
     sig._buf = torch.from_numpy(np.array(data)).cuda()
     sig._ncols = sig._nsamp = data.shape[1]
-    plane = _backend().dedisperse(sig, DMS13)
+    plane = kh.backend().dedisperse(sig, DMS13)
     assert isinstance(plane, DedispersedPlane)
     T = data.shape[1] - md
     assert tuple(plane.data.shape) == (13, T) and plane.data.dtype == torch.float32 and plane.data.is_cuda
@@ -267,7 +236,7 @@ def test_api_on_a_search_mode_signal(hip_lib):
     part = FilterBankSignal(1400, 400, Nsubband=64, sample_rate=0.01, fold=False, shard=(16, 48))
     part._buf = torch.from_numpy(np.array(data[16:48])).cuda()
     part._ncols = part._nsamp = data.shape[1]
-    pp = _backend().dedisperse(part, DMS13)
+    pp = kh.backend().dedisperse(part, DMS13)
     assert np.array_equal(pp.delays, tab[:, 16:48])
     mdp = int(tab[:, 16:48].max())
     assert np.array_equal(pp.data.cpu().numpy().astype(np.float64), oracle(data[16:48], tab[:, 16:48], mdp))
@@ -276,7 +245,7 @@ def test_api_on_a_search_mode_signal(hip_lib):
 def test_api_accepts_the_channelised_signal(hip_lib):
     import torch
     from psrsigsim_amd.signal import BasebandSignal
-    be = _backend()
+    be = kh.backend()
     bb = BasebandSignal(1400, 0.512, Nchan=2)
     n = 32 * 300 + 7
     g = torch.Generator(device="cuda").manual_seed(7)
@@ -313,7 +282,7 @@ def test_injected_dm_is_recovered(hip_lib):
     psr.make_pulses(sig, tobs=1.6384)
     ISM().disperse(sig, 30)
     assert tuple(sig.data.shape) == (64, 16384)
-    plane = _backend().dedisperse(sig, DMS13)
+    plane = kh.backend().dedisperse(sig, DMS13)
     assert tuple(plane.data.shape) == (13, 16384 - 749)
     var = plane.data.double().var(dim=1).cpu().numpy()
     order = np.argsort(var)

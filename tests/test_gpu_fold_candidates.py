@@ -22,6 +22,8 @@ import numpy as np
 import pytest
 
 from tests import fold_ref as ref
+from tests import kernel_harness as kh
+from tests.kernel_harness import engine_seed_restored  # noqa: F401 (autouse here)
 
 pytestmark = pytest.mark.gpu
 
@@ -78,18 +80,11 @@ def _case(name):
     raise KeyError(name)
 
 
-_REF = {}
-
-
+@kh.once
 def reference(name):
     """A case and its float64 oracle (out, hits), computed once and shared (read-only)."""
-    if name not in _REF:
-        c = _case(name)
-        out, hits, _ = ref.fold_series(c["x"], c["src"], c["inc"], c["phi0"], c["nsub"], c["L"], c["nbin"])
-        for a in (c["x"], out, hits):
-            a.setflags(write=False)
-        _REF[name] = (c, out, hits)
-    return _REF[name]
+    c = _case(name)
+    return (c,) + ref.fold_series(c["x"], c["src"], c["inc"], c["phi0"], c["nsub"], c["L"], c["nbin"])[:2]
 
 
 def _u64(vals):
@@ -98,9 +93,9 @@ def _u64(vals):
 
 
 def run_kernel(hip_lib, x, src, inc, phi0, nsub, L, nbin, ld=None, in_off=0, out_off=0, want_hits=True, nser=None):
-    """pss_fold_series on views inside larger tensors: ``x`` sits behind a
-    guard of at least five rows (+ in_off floats) with row stride ld, ``out``
-    and ``hits`` at float offset 64 + out_off of theirs.  Returns (out, hits)
+    """pss_fold_series on views inside larger tensors (tests/kernel_harness.py):
+    ``x`` with row stride ld behind a guard of at least five rows (+ in_off
+    floats), ``out`` and ``hits`` flat.  Returns (out, hits)
     [nrows][nsub][nbin] after checking that nothing outside them was written."""
     import torch
     from psrsigsim_amd import _lib
@@ -109,30 +104,22 @@ def run_kernel(hip_lib, x, src, inc, phi0, nsub, L, nbin, ld=None, in_off=0, out
     nrows = len(src)
     ld = T + 5 if ld is None else ld
     assert ld > T
-    lead = max(8192, 5 * ld) + in_off
-    parent = torch.full((lead + n * ld + max(8192, 5 * ld),), IN_GUARD, dtype=torch.float32, device="cuda")
-    view = parent[lead:lead + n * ld].view(n, ld)
-    view[:, :T] = torch.from_numpy(np.array(x, dtype=np.float32)).cuda()
+    xin = kh.GuardedInput(x, ld, in_off, IN_GUARD, pad=max(kh.IN_PAD, 5 * ld))
     tot = nrows * nsub * nbin
-    olead = 64 + out_off
-    oparent = torch.full((olead + tot + 64,), OUT_GUARD, dtype=torch.float32, device="cuda")
-    hparent = torch.full((olead + tot + 64,), HIT_GUARD, dtype=torch.int32, device="cuda")
-    oview, hview = oparent[olead:olead + tot], hparent[olead:olead + tot]
+    out = kh.GuardedOutput(1, tot, out_off=out_off, guard=OUT_GUARD)
+    hits = kh.GuardedOutput(1, tot, out_off=out_off, guard=HIT_GUARD, dtype=np.int32)
     src_d = torch.from_numpy(np.array(src, dtype=np.int32)).cuda()
     inc_d = _u64(inc)
     phi_d = None if phi0 is None else _u64(phi0)
-    rc = hip_lib.pss_fold_series(view.data_ptr(), nser, T, ld, src_d.data_ptr(), inc_d.data_ptr(),
-                                 None if phi_d is None else phi_d.data_ptr(), nrows, nsub, L, nbin, oview.data_ptr(),
-                                 hview.data_ptr() if want_hits else None, None)
+    rc = hip_lib.pss_fold_series(xin.ptr, nser, T, ld, src_d.data_ptr(), inc_d.data_ptr(),
+                                 None if phi_d is None else phi_d.data_ptr(), nrows, nsub, L, nbin, out.ptr,
+                                 hits.ptr if want_hits else None, None)
     _lib.check(rc, "fold_series")
     torch.cuda.synchronize()
-    o, h = oparent.cpu().numpy(), hparent.cpu().numpy()
-    assert (o[:olead] == OUT_GUARD).all() and (o[olead + tot:] == OUT_GUARD).all()
-    assert (h[:olead] == HIT_GUARD).all() and (h[olead + tot:] == HIT_GUARD).all()
     if not want_hits:
-        assert (h == HIT_GUARD).all()
+        hits.untouched()
     shape = (nrows, nsub, nbin)
-    return o[olead:olead + tot].reshape(shape).copy(), h[olead:olead + tot].reshape(shape).copy()
+    return out.read().reshape(shape), hits.read().reshape(shape)
 
 
 def run_case(hip_lib, c, **kw):
@@ -250,24 +237,11 @@ def test_invariance(hip_lib):
 # ---------------------------------------------------------------------------
 # API
 # ---------------------------------------------------------------------------
-@pytest.fixture(autouse=True)
-def _engine_seed_restored():
-    from psrsigsim_amd import _engine
-    saved = dict(_engine._state)
-    yield
-    _engine._state.update(saved)
-
-
-def _backend():
-    from psrsigsim_amd.telescope import Backend
-    return Backend(samprate=0.01, name="B")
-
-
 def test_api_cube_equals_the_oracle_of_the_subband_sums(hip_lib):
     import torch
     from psrsigsim_amd.signal import FilterBankSignal
     from psrsigsim_amd.telescope import Backend, FoldedCandidates
-    be = _backend()
+    be = kh.backend()
     sig = FilterBankSignal(1400, 400, Nsubband=64, sample_rate=0.01, fold=False)
     dms = [0.0, 10.0, 10.0, 5.0]
     ps_want = np.array([7.5, 100.37, 33.3333, 250.25])
@@ -354,7 +328,7 @@ def test_api_end_to_end_pulsar(hip_lib):
     sig = FilterBankSignal(1400, 400, Nsubband=64, sample_rate=0.01, fold=False)
     Pulsar(0.05, 1.0).make_pulses(sig, tobs=1.6384)
     ISM().disperse(sig, 30)
-    be = _backend()
+    be = kh.backend()
     fc = be.fold_candidates(sig, dms=[0, 30, 60], periods=[0.05] * 3, nbin=32, nsub=4, nband=4, stat_block=128)
     assert fc.T == 15635 and fc.max_delay == 749 and fc.L == 15635 // 4
     assert fc.inc == [36893488147419103] * 3 and np.array_equal(fc.period_samples, [500.0] * 3)

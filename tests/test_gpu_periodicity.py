@@ -14,11 +14,15 @@ row included.
 
 The kernel's tile (pss_harmsum.hip): a workgroup owns 2048 bins of one trial.
 """
+import functools
+
 import numpy as np
 import pytest
 
+from tests import kernel_harness as kh
 from tests import periodicity_ref as ref
 from tests import pulse_search_ref as psref
+from tests.kernel_harness import engine_seed_restored, same_bits  # noqa: F401 (the fixture is autouse here)
 
 pytestmark = pytest.mark.gpu
 
@@ -57,30 +61,21 @@ def _case(name):
     raise KeyError(name)
 
 
-_REF = {}
-
-
+@kh.once
 def reference(name, cell):
     """A case and its restatement, computed once and shared (read-only)."""
-    key = (name, cell)
-    if key not in _REF:
-        x, scale, nl, kmin = _case(name)
-        snr, code = ref.harmonic_ref(x, scale, nl, kmin, cell)
-        for a in (x, snr, code):
-            a.setflags(write=False)
-        _REF[key] = (x, scale, nl, kmin, snr, code)
-    return _REF[key]
+    x, scale, nl, kmin = _case(name)
+    return (x, scale, nl, kmin) + ref.harmonic_ref(x, scale, nl, kmin, cell)
 
 
 def run_kernel(hip_lib, x, scale, nl, kmin, cell, ld=None, out_ld=None, in_off=0, out_off=0):
-    """pss_harmonic_search on views inside larger tensors.  ``spec`` sits at
-    float offset 8192 + in_off of its parent (row stride ld complex elements;
-    in_off = 2 is one complex element, in_off = 1 half of one), ``snr`` /
-    ``code`` at 64 + out_off of theirs (row stride out_ld); the rest of the
-    parents are guards, and so are the bins below kmin.  The kernel runs twice,
-    without and with the workspace of its power pass, and must give the same
-    bits.  Returns (snr, code) [ndm][nq] after checking that nothing outside
-    [j][0 .. nq) was written."""
+    """pss_harmonic_search on views inside larger tensors (tests/kernel_harness.py):
+    ``spec`` with row stride ld complex elements between guards (in_off = 2 is
+    one complex element, in_off = 1 half of one), ``snr`` / ``code`` with row
+    stride out_ld; the bins below kmin hold the input guard too.  The kernel
+    runs twice, without and with the workspace of its power pass, and must
+    give the same bits.  Returns (snr, code) [ndm][nq] after checking that
+    nothing outside [j][0 .. nq) was written."""
     import torch
     from psrsigsim_amd import _lib
     ndm, nbin = x.shape
@@ -88,52 +83,29 @@ def run_kernel(hip_lib, x, scale, nl, kmin, cell, ld=None, out_ld=None, in_off=0
     ld = nbin + 5 if ld is None else ld
     out_ld = nq + 3 if out_ld is None else out_ld
     assert ld > nbin and out_ld > nq
-    lead = 8192 + in_off
-    parent = torch.full((lead + 2 * ndm * ld + 8192,), IN_GUARD, dtype=torch.float32, device="cuda")
-    view = parent[lead:lead + 2 * ndm * ld].view(ndm, ld, 2)
     xs = np.array(x, dtype=np.complex64)
     xs[:, :min(kmin, nbin)] = IN_GUARD * (1 + 1j)
-    view[:, :nbin] = torch.from_numpy(xs.view(np.float32).reshape(ndm, nbin, 2)).cuda()
+    spec = kh.GuardedInput(xs.view(np.float32).reshape(ndm, nbin, 2), ld, in_off, IN_GUARD)
     s = torch.from_numpy(np.broadcast_to(np.asarray(scale, dtype=np.float32), (ndm,)).copy()).cuda()
-    olead = 64 + out_off
-    sparent = torch.full((olead + ndm * out_ld + 64,), SNR_GUARD, dtype=torch.float32, device="cuda")
-    cparent = torch.full((olead + ndm * out_ld + 64,), CODE_GUARD, dtype=torch.int32, device="cuda")
-    sview = sparent[olead:olead + ndm * out_ld]
-    cview = cparent[olead:olead + ndm * out_ld]
     res = []
     for with_work in (False, True):
         # the workspace of the power pass: ndm * nbin floats between guards of their own
-        wparent = torch.full((64 + ndm * nbin + 64,), WORK_GUARD, dtype=torch.float32, device="cuda")
-        work = wparent[64:64 + ndm * nbin]
-        sparent.fill_(SNR_GUARD)
-        cparent.fill_(CODE_GUARD)
-        rc = hip_lib.pss_harmonic_search(view.data_ptr(), ndm, nbin, ld, s.data_ptr(), nl, kmin, cell,
-                                         sview.data_ptr(), cview.data_ptr(), out_ld,
-                                         work.data_ptr() if with_work else None, None)
+        work = kh.GuardedOutput(ndm, nbin, guard=WORK_GUARD)
+        snr = kh.GuardedOutput(ndm, nq, out_ld, out_off, SNR_GUARD)
+        code = kh.GuardedOutput(ndm, nq, out_ld, out_off, CODE_GUARD, np.int32)
+        rc = hip_lib.pss_harmonic_search(spec.ptr, ndm, nbin, ld, s.data_ptr(), nl, kmin, cell, snr.ptr, code.ptr,
+                                         out_ld, work.ptr if with_work else None, None)
         _lib.check(rc, "harmonic_search")
         torch.cuda.synchronize()
-        w = wparent.cpu().numpy()
-        assert (w[:64] == WORK_GUARD).all() and (w[64 + ndm * nbin:] == WORK_GUARD).all()
         if not with_work:
-            assert (w == WORK_GUARD).all()
+            work.untouched()
         else:
             # the powers of the bins a sum may read, and nothing below kmin
-            assert (w[64:64 + ndm * nbin].reshape(ndm, nbin)[:, :min(kmin, nbin)] == WORK_GUARD).all()
-        out = []
-        for par, guard in ((sparent, SNR_GUARD), (cparent, CODE_GUARD)):
-            o = par.cpu().numpy()
-            assert (o[:olead] == guard).all() and (o[olead + ndm * out_ld:] == guard).all()
-            rows = o[olead:olead + ndm * out_ld].reshape(ndm, out_ld)
-            assert (rows[:, nq:] == guard).all()                      # nothing written past nq
-            out.append(rows[:, :nq].copy())
-        res.append(out)
+            assert (work.read()[:, :min(kmin, nbin)] == WORK_GUARD).all()
+        res.append((snr.read(), code.read()))
     # with and without the workspace: the same bits
     assert res[0][0].tobytes() == res[1][0].tobytes() and res[0][1].tobytes() == res[1][1].tobytes()
-    return res[0][0], res[0][1]
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    return res[0]
 
 
 EXACT = [("r2500", 16), ("r2500", 2048), ("edges", 32), ("edge-1", 32), ("edge+1", 32), ("edge+1", 512),
@@ -182,16 +154,12 @@ def test_exact_cases_equal_the_restatement(name, cell, hip_lib):
         assert won.all() and np.array_equal(k[0], np.maximum(q, kmin)) and np.array_equal(k[1], k[0])
 
 
+@kh.once
 def _float_case():
-    if "float" not in _REF:
-        rng = np.random.default_rng(23)
-        x = (rng.standard_normal((4, 6000)) + 1j * rng.standard_normal((4, 6000))).astype(np.complex64)
-        scale = rng.uniform(0.5, 2.0, size=4).astype(np.float32)
-        maps = {nl: ref.harmonic_ref(x, scale, nl, 1, 32) for nl in range(1, 6)}
-        x.setflags(write=False)
-        scale.setflags(write=False)
-        _REF["float"] = (x, scale, maps)
-    return _REF["float"]
+    rng = np.random.default_rng(23)
+    x = (rng.standard_normal((4, 6000)) + 1j * rng.standard_normal((4, 6000))).astype(np.complex64)
+    scale = rng.uniform(0.5, 2.0, size=4).astype(np.float32)
+    return x, scale, {nl: ref.harmonic_ref(x, scale, nl, 1, 32) for nl in range(1, 6)}
 
 
 @pytest.mark.parametrize("nl", [1, 2, 3, 4, 5])
@@ -225,13 +193,10 @@ def test_misaligned_views_give_the_same_bits(name, hip_lib):
     na, qa = (nbin + 1) // 2 * 2, (nq + 15) // 16 * 16
     base_s, base_c = run_kernel(hip_lib, x, scale, nl, kmin, 32, ld=na + 2, out_ld=qa + 16)
     assert same_bits(base_s, snr) and np.array_equal(base_c, code)
-    odd = lambda v: v + 1 - (v % 2)
-    for kw in (dict(ld=odd(nbin + 2), out_ld=odd(nq + 2), in_off=2, out_off=1),    # everything off the 16-B grid
-               dict(ld=na + 2, out_ld=qa + 16, in_off=2, out_off=0),              # the base alone
-               dict(ld=odd(nbin + 2), out_ld=qa + 16, in_off=0, out_off=0),       # the row stride alone
-               dict(ld=na + 2, out_ld=odd(nq + 2), in_off=0, out_off=1),          # the maps alone
-               dict(ld=odd(nbin + 2), out_ld=qa + 16, in_off=1, out_off=0),       # 4 B: off the 8-B grid
-               dict(ld=na + 2, out_ld=odd(nq + 2), in_off=3, out_off=1)):
+    odd = kh.odd
+    for kw in list(kh.misaligned_layouts(na + 2, qa + 16, odd(nbin + 2), odd(nq + 2), in_off=2)) + [
+            dict(ld=odd(nbin + 2), out_ld=qa + 16, in_off=1, out_off=0),          # 4 B: off the 8-B grid
+            dict(ld=na + 2, out_ld=odd(nq + 2), in_off=3, out_off=1)]:
         got_s, got_c = run_kernel(hip_lib, x, scale, nl, kmin, 32, **kw)
         assert got_s.tobytes() == base_s.tobytes() and got_c.tobytes() == base_c.tobytes(), kw
 
@@ -268,19 +233,6 @@ def test_special_values(cell, hip_lib):
 # ---------------------------------------------------------------------------
 # API
 # ---------------------------------------------------------------------------
-@pytest.fixture(autouse=True)
-def _engine_seed_restored():
-    from psrsigsim_amd import _engine
-    saved = dict(_engine._state)
-    yield
-    _engine._state.update(saved)
-
-
-def _backend():
-    from psrsigsim_amd.telescope import Backend
-    return Backend(samprate=0.01, name="B")
-
-
 def _plane(x, dms=None):
     import torch
     from psrsigsim_amd.telescope import DedispersedPlane
@@ -290,16 +242,15 @@ def _plane(x, dms=None):
                             0.01, 1500.0, 0)
 
 
+@functools.lru_cache(maxsize=None)
 def _series():
     """5 trials x 4500 samples of Gaussian data with their own mean and sigma."""
-    if "series" not in _REF:
-        rng = np.random.default_rng(31)
-        mean = rng.uniform(-50.0, 200.0, size=5)
-        sigma = rng.uniform(0.3, 30.0, size=5)
-        x = (rng.standard_normal((5, 4500)) * sigma[:, None] + mean[:, None]).astype(np.float32)
-        x.setflags(write=False)
-        _REF["series"] = (x, mean, sigma)
-    return _REF["series"]
+    rng = np.random.default_rng(31)
+    mean = rng.uniform(-50.0, 200.0, size=5)
+    sigma = rng.uniform(0.3, 30.0, size=5)
+    x = (rng.standard_normal((5, 4500)) * sigma[:, None] + mean[:, None]).astype(np.float32)
+    x.setflags(write=False)
+    return x, mean, sigma
 
 
 @pytest.mark.parametrize("nfft", [None, 4096, 9000, 3750])
@@ -310,7 +261,7 @@ def test_dm_spectrum_against_float64(nfft, hip_lib):
     float32 FFT (eps32 = 2^-23)."""
     import torch
     x, mean, _ = _series()
-    be = _backend()
+    be = kh.backend()
     plane = _plane(x)
     n = 4500 if nfft is None else nfft                                # fft_length(4500) = 4500 = 2^2 3^2 5^3
     spec = be.dm_spectrum(plane, nfft=nfft, mean=mean)
@@ -343,7 +294,7 @@ def test_harmonic_snr_user_statistics(hip_lib):
     import torch
     from psrsigsim_amd.telescope import HarmonicPlane
     x, mean, sigma = _series()
-    be = _backend()
+    be = kh.backend()
     plane = _plane(x)
     spec = be.dm_spectrum(plane, mean=mean)
     cells = be.harmonic_snr(plane, nharm=8, cell=64, fmin=3.0, mean=mean, std=sigma, spectrum=spec)
@@ -389,7 +340,7 @@ def test_harmonic_snr_device_statistics_and_zero_padding(hip_lib):
     x = np.array(_series()[0])
     x[3] = 2.5
     plane = _plane(x)
-    be = _backend()
+    be = kh.backend()
     for nfft, n in ((None, 4500), (9000, 9000)):
         cells = be.harmonic_snr(plane, nharm=16, cell=32, nfft=nfft, stat_block=500)
         mean, var = psref.block_median_stats(x, 500)
@@ -434,7 +385,7 @@ def test_synthetic_pulse_train(hip_lib):
     frequency, no candidate lies in trials 0 and 4, and the whole table equals
     the restatement's on the spectrum and the statistics of the device."""
     x = pulse_train()
-    be = _backend()
+    be = kh.backend()
     plane = _plane(x, dms=np.arange(5) * 2.0)
     got = be.periodicity_search(plane, threshold=15)
     print(got.array)
@@ -491,7 +442,7 @@ def test_api_end_to_end_pulsar(hip_lib):
     sig = FilterBankSignal(1400, 400, Nsubband=64, sample_rate=0.01, fold=False)
     Pulsar(0.05, 1.0).make_pulses(sig, tobs=1.6384)
     ISM().disperse(sig, 30)
-    be = _backend()
+    be = kh.backend()
     plane = be.dedisperse(sig, np.arange(0, 65, 5))
     got = be.periodicity_search(plane, stat_block=128)
     per_trial = got.cells.snr.max(dim=1).values.cpu().numpy()

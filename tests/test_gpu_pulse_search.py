@@ -17,7 +17,9 @@ one each; steps of 256 samples and more are summed in registers.
 import numpy as np
 import pytest
 
+from tests import kernel_harness as kh
 from tests import pulse_search_ref as ref
+from tests.kernel_harness import engine_seed_restored, same_bits  # noqa: F401 (the fixture is autouse here)
 
 pytestmark = pytest.mark.gpu
 
@@ -51,27 +53,18 @@ def _case(name):
     raise KeyError(name)
 
 
-_REF = {}
-
-
+@kh.once
 def reference(name, cell):
     """A case and its restatement, computed once and shared (read-only)."""
-    key = (name, cell)
-    if key not in _REF:
-        x, mean, rstd, nw = _case(name)
-        snr, code = ref.boxcar_ref(x, mean, rstd, nw, cell)
-        for a in (x, snr, code):
-            a.setflags(write=False)
-        _REF[key] = (x, mean, rstd, nw, snr, code)
-    return _REF[key]
+    x, mean, rstd, nw = _case(name)
+    return (x, mean, rstd, nw) + ref.boxcar_ref(x, mean, rstd, nw, cell)
 
 
 def run_kernel(hip_lib, x, mean, rstd, nw, cell, ld=None, out_ld=None, in_off=0, out_off=0):
-    """pss_boxcar_search on views inside larger tensors.  ``plane`` sits at
-    float offset 8192 + in_off of its parent (row stride ld), ``snr`` / ``code``
-    at 64 + out_off of theirs (row stride out_ld); the rest of the parents are
-    guards.  Returns (snr, code) [ndm][nq] after checking that nothing outside
-    [j][0 .. nq) was written."""
+    """pss_boxcar_search on views inside larger tensors (tests/kernel_harness.py):
+    ``plane`` with row stride ld between guards, ``snr`` / ``code`` with row
+    stride out_ld.  Returns (snr, code) [ndm][nq] after checking that nothing
+    outside [j][0 .. nq) was written."""
     import torch
     from psrsigsim_amd import _lib
     ndm, T = x.shape
@@ -79,33 +72,16 @@ def run_kernel(hip_lib, x, mean, rstd, nw, cell, ld=None, out_ld=None, in_off=0,
     ld = T + 5 if ld is None else ld
     out_ld = nq + 3 if out_ld is None else out_ld
     assert ld > T and out_ld > nq
-    lead = 8192 + in_off
-    parent = torch.full((lead + ndm * ld + 8192,), IN_GUARD, dtype=torch.float32, device="cuda")
-    view = parent[lead:lead + ndm * ld].view(ndm, ld)
-    view[:, :T] = torch.from_numpy(np.array(x, dtype=np.float32)).cuda()
+    plane = kh.GuardedInput(x, ld, in_off, IN_GUARD)
     m = torch.from_numpy(np.broadcast_to(np.asarray(mean, dtype=np.float32), (ndm,)).copy()).cuda()
     r = torch.from_numpy(np.broadcast_to(np.asarray(rstd, dtype=np.float32), (ndm,)).copy()).cuda()
-    olead = 64 + out_off
-    sparent = torch.full((olead + ndm * out_ld + 64,), SNR_GUARD, dtype=torch.float32, device="cuda")
-    cparent = torch.full((olead + ndm * out_ld + 64,), CODE_GUARD, dtype=torch.int32, device="cuda")
-    sview = sparent[olead:olead + ndm * out_ld]
-    cview = cparent[olead:olead + ndm * out_ld]
-    rc = hip_lib.pss_boxcar_search(view.data_ptr(), ndm, T, ld, m.data_ptr(), r.data_ptr(), nw, cell,
-                                   sview.data_ptr(), cview.data_ptr(), out_ld, None)
+    snr = kh.GuardedOutput(ndm, nq, out_ld, out_off, SNR_GUARD)
+    code = kh.GuardedOutput(ndm, nq, out_ld, out_off, CODE_GUARD, np.int32)
+    rc = hip_lib.pss_boxcar_search(plane.ptr, ndm, T, ld, m.data_ptr(), r.data_ptr(), nw, cell, snr.ptr, code.ptr,
+                                   out_ld, None)
     _lib.check(rc, "boxcar_search")
     torch.cuda.synchronize()
-    out = []
-    for par, guard in ((sparent, SNR_GUARD), (cparent, CODE_GUARD)):
-        o = par.cpu().numpy()
-        assert (o[:olead] == guard).all() and (o[olead + ndm * out_ld:] == guard).all()
-        rows = o[olead:olead + ndm * out_ld].reshape(ndm, out_ld)
-        assert (rows[:, nq:] == guard).all()                      # nothing written past nq
-        out.append(rows[:, :nq].copy())
-    return out[0], out[1]
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    return snr.read(), code.read()
 
 
 EXACT = [("one", 16), ("ragged", 32), ("t2049", 32), ("t2047", 32), ("plateau", 32)] + \
@@ -137,18 +113,14 @@ def test_exact_cases_equal_the_restatement(name, cell, hip_lib):
         assert got_s[1, q] == 448.0 and got_c[1, q] == (12 << 16) | (1000 - q * cell)
 
 
+@kh.once
 def _float_case():
-    if "float" not in _REF:
-        rng = np.random.default_rng(17)
-        mean = rng.uniform(-50.0, 200.0, size=17).astype(np.float32)
-        sigma = rng.uniform(0.3, 30.0, size=17)
-        rstd = (1.0 / sigma).astype(np.float32)
-        x = (rng.standard_normal((17, 5000)) * sigma[:, None] + mean[:, None].astype(np.float64)).astype(np.float32)
-        snr, code = ref.boxcar_ref(x, mean, rstd, 10, 32)
-        for a in (x, mean, rstd, snr, code):
-            a.setflags(write=False)
-        _REF["float"] = (x, mean, rstd, snr, code)
-    return _REF["float"]
+    rng = np.random.default_rng(17)
+    mean = rng.uniform(-50.0, 200.0, size=17).astype(np.float32)
+    sigma = rng.uniform(0.3, 30.0, size=17)
+    rstd = (1.0 / sigma).astype(np.float32)
+    x = (rng.standard_normal((17, 5000)) * sigma[:, None] + mean[:, None].astype(np.float64)).astype(np.float32)
+    return (x, mean, rstd) + ref.boxcar_ref(x, mean, rstd, 10, 32)
 
 
 def test_float_data_bitwise(hip_lib):
@@ -177,11 +149,7 @@ def test_misaligned_views_give_the_same_bits(name, hip_lib):
     Ta, qa = (T + 3) // 4 * 4, (nq + 15) // 16 * 16
     base_s, base_c = run_kernel(hip_lib, x, mean, rstd, nw, 32, ld=Ta + 4, out_ld=qa + 16)
     assert same_bits(base_s, snr) and np.array_equal(base_c, code)
-    odd = lambda v: v + 1 - (v % 2)
-    for kw in (dict(ld=odd(T + 2), out_ld=odd(nq + 2), in_off=1, out_off=1),     # everything off the grid
-               dict(ld=Ta + 4, out_ld=qa + 16, in_off=1, out_off=0),            # the base alone
-               dict(ld=odd(T + 2), out_ld=qa + 16, in_off=0, out_off=0),        # the row stride alone
-               dict(ld=Ta + 4, out_ld=odd(nq + 2), in_off=0, out_off=1)):       # the outputs alone
+    for kw in kh.misaligned_layouts(Ta + 4, qa + 16, kh.odd(T + 2), kh.odd(nq + 2)):
         got_s, got_c = run_kernel(hip_lib, x, mean, rstd, nw, 32, **kw)
         assert got_s.tobytes() == base_s.tobytes() and got_c.tobytes() == base_c.tobytes(), kw
 
@@ -213,19 +181,6 @@ def test_special_values(cell, hip_lib):
 # ---------------------------------------------------------------------------
 # API
 # ---------------------------------------------------------------------------
-@pytest.fixture(autouse=True)
-def _engine_seed_restored():
-    from psrsigsim_amd import _engine
-    saved = dict(_engine._state)
-    yield
-    _engine._state.update(saved)
-
-
-def _backend():
-    from psrsigsim_amd.telescope import Backend
-    return Backend(samprate=0.01, name="B")
-
-
 def _signal(data):
     import torch
     from psrsigsim_amd.signal import FilterBankSignal
@@ -238,7 +193,7 @@ def _signal(data):
 def test_api_with_user_statistics(hip_lib):
     import torch
     from psrsigsim_amd.telescope import BoxcarPlane
-    be = _backend()
+    be = kh.backend()
     data = np.random.default_rng(8).integers(0, 16, size=(64, 4096)).astype(np.float32)
     plane = be.dedisperse(_signal(data), DMS13)
     T = 4096 - 749
@@ -281,7 +236,7 @@ def test_api_device_statistics(hip_lib):
     x[:, 4400:] += 1000.0                                          # past the last whole block of 400
     plane = DedispersedPlane(torch.from_numpy(x).cuda(), np.arange(5.0), np.zeros((5, 1), dtype=np.int32), 0.01,
                              1500.0, 0)
-    cells = _backend().boxcar_snr(plane, nwidths=4, cell=32, stat_block=400)
+    cells = kh.backend().boxcar_snr(plane, nwidths=4, cell=32, stat_block=400)
     mean, var = ref.block_median_stats(x, 400)
     got_m, got_s = cells.mean.cpu().numpy(), cells.std.cpu().numpy()
     print("mean diff", np.abs(got_m - mean).max(), "variance diff", np.abs(got_s ** 2 - var).max())
@@ -322,7 +277,7 @@ def test_api_three_bursts(hip_lib):
     cell.  The device must then give the same 3 (dm_index, time, width) and
     S/N within 1e-5 relative: two float32 roundings (mean, rstd; 2^-24 each)
     propagated, not a measured number."""
-    be = _backend()
+    be = kh.backend()
     plane = be.dedisperse(_signal(three_bursts()), DMS13)
     x = plane.data.cpu().numpy()
     want, snr, code = ref.search_ref(x, 9.0, 8, 32)
@@ -370,7 +325,7 @@ def test_api_end_to_end_pulsar(hip_lib):
     sig = FilterBankSignal(1400, 400, Nsubband=64, sample_rate=0.01, fold=False)
     Pulsar(0.05, 1.0).make_pulses(sig, tobs=1.6384)
     ISM().disperse(sig, 30)
-    be = _backend()
+    be = kh.backend()
     plane = be.dedisperse(sig, DMS13)
     got = be.single_pulse_search(plane, threshold=6.0)
     n = len(got)

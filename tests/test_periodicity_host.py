@@ -4,18 +4,12 @@ C ABI's argument checks, which precede any launch, the clustering on the
 fundamental and the candidate table against an all-pairs restatement, the
 false-alarm probability, and the float32 restatement of the kernel itself
 (tests/periodicity_ref.py) on a hand-computed row."""
-import ctypes
-
 import numpy as np
 import pytest
 
 from psrsigsim_amd import _lib
 from tests import periodicity_ref as ref
-
-
-def _backend():
-    from psrsigsim_amd.telescope import Backend
-    return Backend(samprate=0.01, name="B")
+from tests.kernel_harness import backend as _backend, check_rejections, host_pointer
 
 
 class _StubData(object):
@@ -126,20 +120,12 @@ def test_fft_length_equals_brute_force():
 def test_cabi_rejections():
     """NULL pointers and each out-of-range scalar return PSS_EINVAL with the
     argument named and no device touched."""
-    L = _lib.load()
-    host = (ctypes.c_float * 64)()
-    p = ctypes.cast(host, ctypes.c_void_p)
-    E = _lib.PSS_EINVAL
+    p = host_pointer()
     # pss_harmonic_search(spec, ndm, nbin, ld, scale, nl, kmin, cell, snr, code, out_ld, work, stream)
     good = dict(spec=p, ndm=3, nbin=1000, ld=1001, scale=p, nl=5, kmin=1, cell=32, snr=p, code=p, out_ld=32,
                 work=None)
-
-    def call(**kw):
-        a = dict(good, **kw)
-        return L.pss_harmonic_search(a["spec"], a["ndm"], a["nbin"], a["ld"], a["scale"], a["nl"], a["kmin"],
-                                     a["cell"], a["snr"], a["code"], a["out_ld"], a["work"], None)
-
-    for kw, word in ((dict(spec=None, work=p), "spec"), (dict(nl=0, work=p), "nl 0"), (dict(ndm=0, work=p), "ndm 0"),(dict(spec=None), "spec"), (dict(scale=None), "scale"), (dict(snr=None), "snr"),
+    check_rejections(_lib.load().pss_harmonic_search, good,
+                    ((dict(spec=None, work=p), "spec"), (dict(nl=0, work=p), "nl 0"), (dict(ndm=0, work=p), "ndm 0"),(dict(spec=None), "spec"), (dict(scale=None), "scale"), (dict(snr=None), "snr"),
                      (dict(code=None), "code"),
                      (dict(ndm=0), "ndm 0"), (dict(ndm=-2), "ndm -2"),
                      (dict(nbin=0), "nbin 0"), (dict(nbin=-1, ld=0), "nbin -1"),
@@ -152,10 +138,8 @@ def test_cabi_rejections():
                      (dict(out_ld=31), "out_ld 31"), (dict(cell=16, out_ld=62), "out_ld 62"),
                      (dict(nbin=1025, ld=1025, out_ld=32), "out_ld 32"),
                      # the launch grid: ceil(nbin / 2048) * ndm workgroups in 31 bits
-                     (dict(nbin=1 << 27, ld=1 << 27, out_ld=1 << 27, ndm=1 << 16), "workgroups")):
-        assert call(**kw) == E, kw
-        assert word in _lib.last_error(), (kw, _lib.last_error())
-        assert "harmonic_search" in _lib.last_error()
+                     (dict(nbin=1 << 27, ld=1 << 27, out_ld=1 << 27, ndm=1 << 16), "workgroups")),
+                     prefix="harmonic_search")
 
 
 def test_wiring():

@@ -3,18 +3,12 @@
 launch, the friends-of-friends clustering against an all-pairs restatement,
 the candidates' order, and the float32 restatement of the kernel itself
 (tests/pulse_search_ref.py) on a hand-computed row."""
-import ctypes
-
 import numpy as np
 import pytest
 
 from psrsigsim_amd import _lib
 from tests import pulse_search_ref as ref
-
-
-def _backend():
-    from psrsigsim_amd.telescope import Backend
-    return Backend(samprate=0.01, name="B")
+from tests.kernel_harness import backend as _backend, check_rejections, host_pointer
 
 
 class _StubData(object):
@@ -104,19 +98,11 @@ def test_rejections_never_reach_the_device(monkeypatch):
 def test_cabi_rejections():
     """NULL pointers and each out-of-range scalar return PSS_EINVAL with the
     argument named and no device touched."""
-    L = _lib.load()
-    host = (ctypes.c_float * 64)()
-    p = ctypes.cast(host, ctypes.c_void_p)
-    E = _lib.PSS_EINVAL
+    p = host_pointer()
     # pss_boxcar_search(plane, ndm, T, ld, mean, rstd, nw, cell, snr, code, out_ld, stream)
     good = dict(plane=p, ndm=3, T=1000, ld=1000, mean=p, rstd=p, nw=8, cell=32, snr=p, code=p, out_ld=32)
-
-    def call(**kw):
-        a = dict(good, **kw)
-        return L.pss_boxcar_search(a["plane"], a["ndm"], a["T"], a["ld"], a["mean"], a["rstd"], a["nw"], a["cell"],
-                                   a["snr"], a["code"], a["out_ld"], None)
-
-    for kw, word in ((dict(plane=None), "plane"), (dict(mean=None), "mean"), (dict(rstd=None), "rstd"),
+    check_rejections(_lib.load().pss_boxcar_search, good,
+                    ((dict(plane=None), "plane"), (dict(mean=None), "mean"), (dict(rstd=None), "rstd"),
                      (dict(snr=None), "snr"), (dict(code=None), "code"),
                      (dict(ndm=0), "ndm 0"), (dict(ndm=-2), "ndm -2"),
                      (dict(T=0), "T 0"), (dict(T=-1, ld=0), "T -1"),
@@ -127,10 +113,7 @@ def test_cabi_rejections():
                      (dict(out_ld=31), "out_ld 31"), (dict(cell=16, out_ld=62), "out_ld 62"),
                      (dict(T=1025, ld=1025, out_ld=32), "out_ld 32"),
                      # the launch grid: ceil(T / 2048) * ndm workgroups in 31 bits
-                     (dict(T=1 << 40, ld=1 << 40, out_ld=1 << 40, ndm=64), "workgroups")):
-        assert call(**kw) == E, kw
-        assert word in _lib.last_error(), (kw, _lib.last_error())
-        assert "boxcar_search" in _lib.last_error()
+                     (dict(T=1 << 40, ld=1 << 40, out_ld=1 << 40, ndm=64), "workgroups")), prefix="boxcar_search")
 
 
 def test_wiring():

@@ -3,7 +3,6 @@ writer, the argument checks that come before any GPU work, ``read_search_data``
 on a file assembled by hand (known codes at 8, 4 and 2 bits: the codes, the
 values code * DAT_SCL + DAT_OFFS and the channel order inside a byte), and
 the C ABI's rejections through ctypes (as tests/test_cabi.py does)."""
-import ctypes
 import os
 
 import numpy as np
@@ -13,6 +12,7 @@ from psrsigsim_amd import _lib
 from psrsigsim_amd._units import Quantity
 from psrsigsim_amd.io import PSRFITS, read_search_data
 from psrsigsim_amd.io.psrfits import _card, _header
+from tests.kernel_harness import check_rejections, host_pointer
 
 TEMPLATE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "data",
                         "B1855+09.L-wide.PUPPI.11y.x.sum.sm")
@@ -141,33 +141,26 @@ def test_cabi_rejections():
     not fill whole bytes return PSS_EINVAL with no device touched; work of
     size zero returns PSS_OK without a launch."""
     L = _lib.load()
-    host = (ctypes.c_float * 64)()
-    p = ctypes.cast(host, ctypes.c_void_p)
-    E = _lib.PSS_EINVAL
+    p = host_pointer()
     # pss_chan_stats(data, nchan, ld, nsblk, nrows, mn, mx, sum, sumsq, stream)
-    assert L.pss_chan_stats(None, 2, 100, 10, 2, p, p, p, p, None) == E
-    assert L.pss_chan_stats(p, 2, 100, 10, 2, None, p, p, p, None) == E
-    assert L.pss_chan_stats(p, 2, 100, 10, 2, p, p, p, None, None) == E
-    assert L.pss_chan_stats(p, 2, 19, 10, 2, p, p, p, p, None) == E               # ld < nrows * nsblk
-    assert "ld 19" in _lib.last_error()
-    assert L.pss_chan_stats(p, 2, 100, 0, 2, p, p, p, p, None) == E               # nsblk < 1
-    assert L.pss_chan_stats(p, 65536, 100, 10, 2, p, p, p, p, None) == E
+    good = dict(data=p, nchan=2, ld=100, nsblk=10, nrows=2, mn=p, mx=p, sum=p, sumsq=p)
+    check_rejections(L.pss_chan_stats, good,
+                     ((dict(data=None), ""), (dict(mn=None), ""), (dict(sumsq=None), ""),
+                      (dict(ld=19), "ld 19"),                                     # ld < nrows * nsblk
+                      (dict(nsblk=0), ""),                                        # nsblk < 1
+                      (dict(nchan=65536), "")))
     assert L.pss_chan_stats(p, 2, 100, 10, 0, p, p, p, p, None) == _lib.PSS_OK    # no rows
     assert L.pss_chan_stats(p, 0, 100, 10, 2, p, p, p, p, None) == _lib.PSS_OK    # no channels
     # pss_quantize_tmajor(data, nchan, ld, nsblk, nrows, scl, offs, nbits, out, stream)
-    assert L.pss_quantize_tmajor(None, 2, 100, 10, 2, p, p, 8, p, None) == E
-    assert L.pss_quantize_tmajor(p, 2, 100, 10, 2, None, p, 8, p, None) == E
-    assert L.pss_quantize_tmajor(p, 2, 100, 10, 2, p, None, 8, p, None) == E
-    assert L.pss_quantize_tmajor(p, 2, 100, 10, 2, p, p, 8, None, None) == E
-    assert L.pss_quantize_tmajor(p, 2, 19, 10, 2, p, p, 8, p, None) == E          # ld < nrows * nsblk
-    assert L.pss_quantize_tmajor(p, 2, 100, 10, 2, p, p, 3, p, None) == E         # nbits = 3
-    assert "nbits 3" in _lib.last_error()
-    assert L.pss_quantize_tmajor(p, 2, 100, 10, 2, p, p, 16, p, None) == E
-    assert L.pss_quantize_tmajor(p, 3, 100, 10, 2, p, p, 4, p, None) == E         # 12 bits per sample
-    assert L.pss_quantize_tmajor(p, 2, 100, 10, 2, p, p, 2, p, None) == E         # 4 bits per sample
-    assert "whole bytes" in _lib.last_error()
-    assert L.pss_quantize_tmajor(p, 2, 100, 0, 2, p, p, 8, p, None) == E          # nsblk < 1
-    assert L.pss_quantize_tmajor(p, 65536, 100, 10, 2, p, p, 8, p, None) == E
+    good = dict(data=p, nchan=2, ld=100, nsblk=10, nrows=2, scl=p, offs=p, nbits=8, out=p)
+    check_rejections(L.pss_quantize_tmajor, good,
+                     ((dict(data=None), ""), (dict(scl=None), ""), (dict(offs=None), ""), (dict(out=None), ""),
+                      (dict(ld=19), ""),                                          # ld < nrows * nsblk
+                      (dict(nbits=3), "nbits 3"), (dict(nbits=16), ""),
+                      (dict(nchan=3, nbits=4), ""),                               # 12 bits per sample
+                      (dict(nchan=2, nbits=2), "whole bytes"),                    # 4 bits per sample
+                      (dict(nsblk=0), ""),                                        # nsblk < 1
+                      (dict(nchan=65536), "")))
     assert L.pss_quantize_tmajor(p, 2, 100, 10, 0, p, p, 8, p, None) == _lib.PSS_OK
 
 
