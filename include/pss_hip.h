@@ -428,6 +428,41 @@ int pss_dedisperse(const float *data, int32_t nchan, int64_t n, int64_t ld, cons
                    int32_t ndm, int32_t max_delay, float *out, int64_t out_ld, void *stream);
 
 /*
+ * RFI excision of a search-mode filterbank (extension, no reference
+ * counterpart): data[nchan][ld] float32 (n samples per row), mask[nblk][nchan]
+ * bytes (non-zero = flagged) over blocks of `block` samples, base[nchan] the
+ * channels' replacement value / baseline, rgood[nblk] = float32(1 / number of
+ * unflagged channels of the block), 0 where there is none (the kernel never
+ * divides; NULL iff zero_dm = 0).  With b(t) = min(t / block, nblk - 1) -- the
+ * ragged tail belongs to the last block -- and good(c, t) = !mask[b(t) *
+ * nchan + c], all arithmetic IEEE float32, every line one rounded operation:
+ *   zero_dm = 0:  out[c][t] = good ? data[c][t] : base[c]
+ *   zero_dm = 1:  S[t]      = sum_{c good} (data[c][t] - base[c])
+ *                 z[t]      = S[t] * rgood[b(t)]
+ *                 out[c][t] = good ? data[c][t] - z[t] : base[c]
+ *                 zser[t]   = z[t]                    (when zser != NULL; [n])
+ * A flagged sample never enters a sum: a NaN or 1e30 in a flagged cell reaches
+ * no output; a NaN in a good cell reaches z[t] and sample t of every good
+ * channel only.  Summation order (a pure function of nchan): the channels are
+ * split into the 8 contiguous ranges [q P, min((q + 1) P, nchan)), P =
+ * ceil(nchan / 8); each range is summed in increasing c into an accumulator
+ * that starts at +0 (flagged cells skipped), and the partial sums A_q are
+ * combined as ((A_0 + A_1) + (A_2 + A_3)) + ((A_4 + A_5) + (A_6 + A_7)).  The
+ * bits depend on neither n, block, the alignment of data / ld / out / out_ld,
+ * zser nor the run.  No atomics, no workspace.  out == data with out_ld == ld
+ * (in place) is allowed and gives the bits of the out-of-place run; nothing is
+ * written outside out[c * out_ld + 0 .. n) and zser[0 .. n).
+ * PSS_EINVAL (nothing launched) on a NULL data, mask, base or out, rgood NULL
+ * with zero_dm = 1, zero_dm not 0 or 1, nchan < 1, n < 1, ld < n, out_ld < n,
+ * block < 1, nblk < 1, (nblk - 1) * block >= n, any other overlap of the
+ * extents of out and data, and when ceil(n / 256) exceeds 2^31 - 1 (the
+ * launch grid).
+ */
+int pss_rfi_clean(const float *data, int32_t nchan, int64_t n, int64_t ld, const uint8_t *mask,
+                  int64_t block, int64_t nblk, const float *base, const float *rgood, int32_t zero_dm,
+                  float *out, int64_t out_ld, float *zser, void *stream);
+
+/*
  * Single-pulse search of a DM-time plane (extension, no reference
  * counterpart): a boxcar matched filter over the widths 2^k, k < nw, of
  * plane[ndm][ld] float32 (T samples per row), normalised per trial by the

@@ -13,12 +13,13 @@ from .periodicity import PeriodicityStage, HarmonicPlane, PeriodCandidates, PERI
 from .periodicity import harmonic_log_fap, period_candidates_from_cells  # noqa: F401
 from .accel import AccelStage, AccelPlane, AccelCandidates, ACCEL_DTYPE, C_M_S  # noqa: F401
 from .fold_candidates import FoldStage, FoldedCandidates, fold_chi2, _fold_best  # noqa: F401
+from .rfi import RfiStage, RfiMask, inject_rfi  # noqa: F401
 
 __all__ = ['Backend', 'DedispersedPlane', 'BoxcarPlane', 'PulseCandidates', 'HarmonicPlane', 'PeriodCandidates',
-           'FoldedCandidates', 'AccelPlane', 'AccelCandidates']
+           'FoldedCandidates', 'AccelPlane', 'AccelCandidates', 'RfiMask', 'inject_rfi']
 
 
-class Backend(ChannelizeStage, DedisperseStage, PulseSearchStage, PeriodicityStage, AccelStage, FoldStage):
+class Backend(ChannelizeStage, RfiStage, DedisperseStage, PulseSearchStage, PeriodicityStage, AccelStage, FoldStage):
     def __init__(self, samprate=None, name=None):
         self._name = name
         self._samprate = make_quant(samprate, "MHz")
