@@ -343,7 +343,7 @@ int run_fourstep(KP &k, hipStream_t st, const float *mask_row) {
     if (k.N1 == 1024 && k.N2 == 4096) {
         // C3: 1024 x 4096 (two 4096-point rows of a pair in 66 KB: two row
         // workgroups per CU; 16-column pass-C blocks, 64-B output segments)
-        return launch_pair<1024, 8, 512, C1kF, C1kF, 4096, 512, C4k, C4k, 256, kBC, kTC>(k, st, mask_row);
+        return launch_pair<Pow2Split<1024, 4096>>(k, st, mask_row);
     }
     return run_fourstep_b(k, st, mask_row);
 }

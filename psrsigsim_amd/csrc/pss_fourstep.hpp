@@ -21,7 +21,6 @@
 //     the block in LDS, on pass A's block width ("C:fast");
 //   * the delayed-null mask table built on a side stream next to pass A, and
 //     applied by the compacted fix-up (k_null_fix_list) after pass C.
-static constexpr int kBC = 16, kTC = 1024;   // LDS-resident fast pass C block / threads (passC_fast)
 
 // ---------------------------------------------------------------------------
 // path 2: four-step, N = N1 * N2, sample n = N2*n1 + n2, bin k = k1 + N1*k2.
@@ -638,7 +637,7 @@ __global__ __launch_bounds__(T, SELF ? 1 : 4) void k_pair_row_seq(KP k) { R::tem
 
 
 // XRS: extra row pitch of the LDS column block (Lds), chosen per kernel for
-// its transposing accesses (xrs_read / xrs_write below).
+// its transposing accesses (xrs_read and ColEngine below).
 template <int N1, int B, int T, typename FWD, typename INV, int XRS = 1>
 struct PairCols;
 
@@ -1420,14 +1419,94 @@ __global__ __launch_bounds__(T, C::kFoldWaves) void k_pairA_fold(KP k) { C::pass
 template <typename C, int T>
 __global__ __launch_bounds__(T, C::kFoldWavesC) void k_pairC_fold(KP k) { C::passC_fold(k); }
 
+// Extra LDS row pitch of the column kernels (tools/lds_banks.py): pass A's
+// spill-store loop reads 4 columns x 16 rows per 32-lane group (a 32/B pitch
+// offset spreads the columns over the 64 read banks); pass C's load loop
+// writes 4 columns x 4 rows per 16-lane group (16/B over the 32 write banks).
+// B < 32: a pitch that is a multiple of 16 complex, so the wave-local column
+// FFTs get the byte-address exchanges (Fft::XB: round 2's 4-complex pad cost
+// ~100 address VALU per lane in pass A); the spill-store loop then reads 32
+// consecutive rows of one 4-column group per 32-lane group (conflict-free at
+// any pitch, passA).
+constexpr int xrs_read(int B) { return B >= 32 ? 1 : 16; }
+
+// ---------------------------------------------------------------------------
+// The splits.  A split N1 x N2 is one type, Split<column engine, row engine>;
+// the launchers below take nothing else.
+// ---------------------------------------------------------------------------
+// Column engine: N1-point columns in blocks of B on T threads, radix lists CF
+// (forward) and CI (inverse).
+template <int N1_, int B_, int T_, typename CF, typename CI>
+struct ColEngine {
+    static constexpr int N1 = N1_, B = B_, T = T_;
+    using PC = PairCols<N1, B, T, CF, CI, xrs_read(B)>;   // pass A, generic pass C
+    // the LDS-resident fast pass C (passC_fast) and the 16-column register-
+    // resident one of the 1024- and 2048-point columns (passC_fast32): the
+    // padded layout (pass C measured 0.5 ms faster on it at C3: its transposes
+    // gain nothing from the swizzle and the XOR addressing costs VALU)
+    using PCFast = PairCols<N1, B, T, CF, CI, -1>;
+    using PCFast32 = PairCols<N1, 16, 512, CF, CI, -1>;
+    // 128 columns per workgroup: the lane-private LDS staging of the column
+    // (N1 x 8 B per lane) then allows ~5 workgroups per CU
+    static constexpr int FB = B > 128 ? 128 : B;
+    using PCFold = PairCols<N1, FB, FB, CF, CI>;
+    using PCNode = PairCols<N1, B, T, CF, CI>;            // the mask table's node shifts
+    using MaskCols = Cols<N1, B, T, CF>;                  // the mask spectrum's forward half
+};
+// Power-of-two columns: B * N1 = 8192 complex per workgroup up to 512 points,
+// 8-column blocks above; column inverses reuse the forward list.
+template <int N1>
+struct Pow2Cols;
+template <> struct Pow2Cols<16> : ColEngine<16, 512, 512, C16, C16> {};
+template <> struct Pow2Cols<32> : ColEngine<32, 256, 512, C32F, C32F> {};
+template <> struct Pow2Cols<64> : ColEngine<64, 128, 512, C64F, C64F> {};
+template <> struct Pow2Cols<128> : ColEngine<128, 64, 512, C128F, C128F> {};
+template <> struct Pow2Cols<256> : ColEngine<256, 32, 512, C256, C256> {};
+template <> struct Pow2Cols<512> : ColEngine<512, 16, 512, C512F, C512F> {};
+template <> struct Pow2Cols<1024> : ColEngine<1024, 8, 512, C1kF, C1kF> {};
+template <> struct Pow2Cols<2048> : ColEngine<2048, 8, 512, C2kF, C2kF> {};
+// Register columns of the mixed-radix splits: one column per thread, B = T.
+template <int N1, typename CF, typename CI, int T>
+using RegCols = ColEngine<N1, T, T, CF, CI>;
+
+// Row engine: the two N2-point rows of a pair on TR threads (PairRows), one
+// row at a time on TS (PairRowsSeq), the mask spectrum's single rows on TRF.
+template <int N2_, int TR_, typename RF, typename RI, int TRF_>
+struct RowEngine {
+    static constexpr int N2 = N2_, TR = TR_, TRF = TRF_;
+    using PR = PairRows<N2, TR, RF, RI>;
+    // 16 values of each row per thread (16384-point rows: 512 threads with
+    // 32 measured 47.8 against 43.9 ms at C5, profiles/r05/r16/)
+    static constexpr int TS = N2 / 16;
+    using PRS = PairRowsSeq<N2, TS, RF, RI>;
+    using MaskRows = Rows<N2, 1, TRF, RF>;
+};
+template <int N2>
+struct RowsOf;
+template <> struct RowsOf<1024> : RowEngine<1024, 128, C1kF, C1kI, 64> {};
+template <> struct RowsOf<2048> : RowEngine<2048, 256, C2kF, C2kI, 128> {};
+template <> struct RowsOf<4096> : RowEngine<4096, 512, C4k, C4k, 256> {};
+template <> struct RowsOf<8192> : RowEngine<8192, 1024, C8kF, C8kI, 512> {};
+template <> struct RowsOf<16384> : RowEngine<16384, 1024, C16kF, C16kI, 1024> {};
+template <> struct RowsOf<2500> : RowEngine<2500, 250, RList<5, 5, 5, 5, 4>, RList<4, 5, 5, 5, 5>, 250> {};
+
+template <typename C, typename R>
+struct Split : C, R {
+    // the mask table's position arithmetic is for N = 2^m (validate() sends
+    // delayed nulls of other lengths to the direct path)
+    static constexpr bool kMaskTable = (C::N1 & (C::N1 - 1)) == 0 && R::N2 <= 8192;
+};
+template <int N1, int N2>
+using Pow2Split = Split<Pow2Cols<N1>, RowsOf<N2>>;
+
 // Mask table of a delayed null (see the comment above KCH): mask spectrum,
 // KCH node shifts (KCH/2 pair rows through the row and column engines),
 // Chebyshev coefficients + classification.  Once per run, channel independent.
-template <int N1, int B, int T, typename CF, typename CI, int N2, int TR, typename RF, typename RI,
-          int TRF>
+template <typename S>
 static inline int build_mask_table(KP &k, hipStream_t st, const float *mask_row, char *w, const WsLayout &L) {
-    using PC = PairCols<N1, B, T, CF, CI>;
-    using PR = PairRows<N2, TR, RF, RI>;
+    constexpr int N1 = S::N1, N2 = S::N2, B = S::B, T = S::T, TR = S::TR, TRF = S::TRF;
+    using PC = typename S::PCNode;
+    using PR = typename S::PR;
     cf *mspec = reinterpret_cast<cf *>(w + L.mspec);
     uint32_t *counter = reinterpret_cast<uint32_t *>(w + L.misc);
     uint64_t *nramp = reinterpret_cast<uint64_t *>(w + L.misc + 64);
@@ -1445,8 +1524,8 @@ static inline int build_mask_table(KP &k, hipStream_t st, const float *mask_row,
     km.p.null_mode = PSS_NULL_NONE;
     km.p.data_in_fft = 1;
     km.p.work = mspec;
-    using C1 = Cols<N1, B, T, CF>;
-    using R1 = Rows<N2, 1, TRF, RF>;
+    using C1 = typename S::MaskCols;
+    using R1 = typename S::MaskRows;
     k_colA<C1, T><<<dim3((unsigned)(N2 / B), 1), dim3(T), 0, st>>>(km);
     LAUNCHCHK();
     k_row<R1, TRF><<<dim3((unsigned)N1, 1), dim3(TRF), 0, st>>>(km);
@@ -1497,20 +1576,11 @@ static inline int build_mask_table(KP &k, hipStream_t st, const float *mask_row,
     return PSS_OK;
 }
 
-// Extra LDS row pitch of the column kernels (tools/lds_banks.py): pass A's
-// spill-store loop reads 4 columns x 16 rows per 32-lane group (a 32/B pitch
-// offset spreads the columns over the 64 read banks); pass C's load loop
-// writes 4 columns x 4 rows per 16-lane group (16/B over the 32 write banks).
-// B < 32: a pitch that is a multiple of 16 complex, so the wave-local column
-// FFTs get the byte-address exchanges (Fft::XB: round 2's 4-complex pad cost
-// ~100 address VALU per lane in pass A); the spill-store loop then reads 32
-// consecutive rows of one 4-column group per 32-lane group (conflict-free at
-// any pitch, passA).
-constexpr int xrs_read(int B) { return B >= 32 ? 1 : 16; }
-// (pass C measured 0.5 ms faster on the padded layout at C3: its transposes
-// gain nothing from the swizzle and the XOR addressing costs VALU)
-constexpr int xrs_write(int B) { return -1; }
-
+// The device's side streams.  Only s[0] (the mask table's) and the events 30
+// (fork from the main stream) and 31 (table ready) are in use; allocating
+// just those measured inside the C3 step's run-to-run spread in two jobs of
+// three and 0.1-0.2 ms above it in one (profiles/fourstep_launcher/), so the
+// allocation stays as it was.
 struct SideStreams {
     hipStream_t s[2];
     hipEvent_t ev[40];
@@ -1518,9 +1588,22 @@ struct SideStreams {
 };
 SideStreams *side_streams();
 
-template <int N1, int B, int T, typename CF, typename CI, int N2, int TR, typename RF, typename RI,
-          int TRF, int BC, int TC>
-static int launch_pair_passes(KP &k, hipStream_t st, const float *mask_after_a = nullptr);
+// The mask table on the side stream, forked from st here (ss), or in line on
+// st (no ss); k.mask_ready is what its first reader on st has to wait for.
+template <typename S>
+static int fork_mask_table(KP &k, hipStream_t st, SideStreams *ss, const float *mask_row, char *w, const WsLayout &L) {
+    if (ss) {
+        HIPCHK(hipEventRecord(ss->ev[30], st));
+        HIPCHK(hipStreamWaitEvent(ss->s[0], ss->ev[30], 0));
+    }
+    if (const int rc = build_mask_table<S>(k, ss ? ss->s[0] : st, mask_row, w, L)) return rc;
+    if (ss) {
+        HIPCHK(hipEventRecord(ss->ev[31], ss->s[0]));
+        k.mask_ready = ss->ev[31];
+    }
+    return PSS_OK;
+}
+
 // Channel count up to which the side-stream mask table forks after pass A
 // (beside the row pass) instead of before it (beside pass A): it costs the
 // pass it runs beside ~0.4 ms either way, which at 2048 channels is even
@@ -1530,55 +1613,33 @@ static int launch_pair_passes(KP &k, hipStream_t st, const float *mask_after_a =
 // after pass A (6.52-6.56 vs 6.64-6.68 ms, profiles/r06/ab_mask/)
 static constexpr int kMaskAfterANchan = 1024;
 
-// BC/TC: column-block width and threads of the FAST pass C (the spill layout
-// does not depend on the block width, so pass C may use wider blocks than pass
-// A: its output rows are written in BC-sample (4 BC-byte) segments).
-template <int N1, int B, int T, typename CF, typename CI, int N2, int TR, typename RF, typename RI,
-          int TRF, int BC = B, int TC = T>
+// One pair range through a split, top to bottom: [mask table], ramp table,
+// pass A, [mask table], row pass, pass C, [null fix-up].
+template <typename S>
 static int launch_pair(KP &k, hipStream_t st, const float *mask_row) {
-    using PC = PairCols<N1, B, T, CF, CI, xrs_read(B)>;
-    using PCC = PairCols<N1, BC, TC, CF, CI, xrs_write(BC)>;
-    using PR = PairRows<N2, TR, RF, RI>;
+    constexpr int N1 = S::N1, N2 = S::N2, B = S::B, T = S::T, TR = S::TR;
+    using PC = typename S::PC;
+    using PR = typename S::PR;
     plan_note(" %dx%d", N1, N2);
     k.poff = k.p.chan0 & 1;
     k.npairs = (k.p.nchan + k.poff + 1) / 2;
     char *w = reinterpret_cast<char *>(k.p.work);
     const WsLayout L = ws_layout(k.p.nchan, k.N);
     k.Yd = reinterpret_cast<cf *>(w + L.yd);
-    const float *defer_mask = nullptr;
-    if (k.p.null_mode == PSS_NULL_DELAYED) {
-        // the mask table's position arithmetic is for N = 2^m (validate()
-        // sends delayed nulls of other lengths to the direct path)
-        if constexpr ((N1 & (N1 - 1)) == 0 && N2 <= 8192) {
-            // With the data in the FFT and the fast passes, nothing reads the
-            // table before the null fix-up: build it on a side stream next to
-            // pass A (its dozen small launches then cost no time on the main
-            // stream); the fix-up waits for it.
-            SideStreams *ss = k.p.data_in_fft ? side_streams() : nullptr;
-            if (ss && k.p.nchan <= kMaskAfterANchan) {
-                defer_mask = mask_row;            // built by launch_pair_passes after pass A
-                goto mask_done;
-            }
-            hipStream_t ms = st;
-            if (ss) {
-                HIPCHK(hipEventRecord(ss->ev[30], st));
-                HIPCHK(hipStreamWaitEvent(ss->s[0], ss->ev[30], 0));
-                ms = ss->s[0];
-            }
-            {
-                const int rc = build_mask_table<N1, B, T, CF, CI, N2, TR, RF, RI, TRF>(k, ms, mask_row, w, L);
-                if (rc) return rc;
-            }
-            if (ss) {
-                HIPCHK(hipEventRecord(ss->ev[31], ms));
-                k.mask_ready = ss->ev[31];
-            }
-        } else {
-            return fail(PSS_EUNSUPPORTED, "delayed null on the mixed-radix or 16384-row four-step (N=%lld)",
-                        (long long)k.N);
-        }
+    const bool table = k.p.null_mode == PSS_NULL_DELAYED;
+    if (table && !S::kMaskTable)
+        return fail(PSS_EUNSUPPORTED, "delayed null on the mixed-radix or 16384-row four-step (N=%lld)",
+                    (long long)k.N);
+    // With the data in the FFT and the fast passes, nothing reads the table
+    // before the null fix-up: build it on a side stream next to pass A or the
+    // row pass (its dozen small launches then cost no time on the main
+    // stream); the fix-up waits for it.
+    SideStreams *ss = table && k.p.data_in_fft ? side_streams() : nullptr;
+    const bool table_after_a = ss && k.p.nchan <= kMaskAfterANchan;
+    if constexpr (S::kMaskTable) {
+        if (table && !table_after_a)
+            if (const int rc = fork_mask_table<S>(k, st, ss, mask_row, w, L)) return rc;
     }
-mask_done:
     if (!k.p.data_in_fft) {
         // only the null mask was delayed: one elementwise pass with table lookups
         return launch_elementwise(k, st);
@@ -1590,150 +1651,118 @@ mask_done:
         LAUNCHCHK();
         k.rtab = rt;
     }
-    return launch_pair_passes<N1, B, T, CF, CI, N2, TR, RF, RI, TRF, BC, TC>(k, st, defer_mask);
-}
 
-// The passes of one pair range (after the mask table and the ramp table).
-template <int N1, int B, int T, typename CF, typename CI, int N2, int TR, typename RF, typename RI,
-          int TRF, int BC, int TC>
-static int launch_pair_passes(KP &k, hipStream_t st, const float *mask_after_a) {
-    using PC = PairCols<N1, B, T, CF, CI, xrs_read(B)>;
-    using PCC = PairCols<N1, BC, TC, CF, CI, xrs_write(BC)>;
-    using PR = PairRows<N2, TR, RF, RI>;
-    dim3 gc((unsigned)(N2 / B), (unsigned)k.npairs);
+    const dim3 gc((unsigned)(N2 / B), (unsigned)k.npairs);
     tk_begin(TK_COLA, st);
-    bool launched = false;
-    if constexpr (PC::kRegCols) {
-        if (fold_source(k.p)) {
-            k_pairA_fold<PC, T><<<gc, dim3(T), 0, st>>>(k);
-            plan_note(" A:fold");
-            launched = true;
+    // (each `if constexpr` keeps a kernel the column engine does not have
+    // from being instantiated; its branch is not reached then)
+    const bool fold_a = PC::kRegCols && fold_source(k.p);
+    const bool fast_a = !fold_a && PC::kItemsExact && fast_source(k.p);
+    if (fold_a) {
+        if constexpr (PC::kRegCols) k_pairA_fold<PC, T><<<gc, dim3(T), 0, st>>>(k);
+        plan_note(" A:fold");
+    } else if (fast_a && k.p.prof_rows == 1) {
+        // the shared profile at every sample, once per run (PairCols::prof_cols)
+        if constexpr (PC::kItemsExact) {
+            float4 *pcol = reinterpret_cast<float4 *>(w + L.pcol);
+            const int64_t ne = k.N / 4;
+            k_prof_cols<PC><<<dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st>>>(k, pcol);
+            LAUNCHCHK();
+            k.pcol = pcol;
+            k_pairA_fast<PC, T, true><<<gc, dim3(T), 0, st>>>(k);
         }
-    }
-    if (launched) {
-    } else if constexpr (PC::kItemsExact) {
-        if (fast_source(k.p)) {
-            if (k.p.prof_rows == 1) {
-                // the shared profile at every sample, once per run (PairCols::prof_cols)
-                float4 *pcol = reinterpret_cast<float4 *>(reinterpret_cast<char *>(k.p.work) +
-                                                          ws_layout(k.p.nchan, k.N).pcol);
-                const int64_t ne = k.N / 4;
-                k_prof_cols<PC><<<dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st>>>(k, pcol);
-                LAUNCHCHK();
-                k.pcol = pcol;
-                k_pairA_fast<PC, T, true><<<gc, dim3(T), 0, st>>>(k);
-            } else {
-                k_pairA_fast<PC, T, false><<<gc, dim3(T), 0, st>>>(k);
-            }
-            plan_note(k.p.prof_rows == 1 ? " A:fast_shared" : " A:fast");
-        } else {
-            k_pairA<PC, T><<<gc, dim3(T), 0, st>>>(k);
-            plan_note(" A:generic");
-        }
+        plan_note(" A:fast_shared");
+    } else if (fast_a) {
+        if constexpr (PC::kItemsExact) k_pairA_fast<PC, T, false><<<gc, dim3(T), 0, st>>>(k);
+        plan_note(" A:fast");
     } else {
         k_pairA<PC, T><<<gc, dim3(T), 0, st>>>(k);
         plan_note(" A:generic");
     }
     tk_end(st);
     LAUNCHCHK();
-    if constexpr ((N1 & (N1 - 1)) == 0 && N2 <= 8192) {
-        if (mask_after_a) {
-            // (kMaskAfterANchan) the mask table on the side stream from here
-            SideStreams *ss = side_streams();
-            char *w = reinterpret_cast<char *>(k.p.work);
-            const WsLayout L = ws_layout(k.p.nchan, k.N);
-            HIPCHK(hipEventRecord(ss->ev[30], st));
-            HIPCHK(hipStreamWaitEvent(ss->s[0], ss->ev[30], 0));
-            const int rc = build_mask_table<N1, B, T, CF, CI, N2, TR, RF, RI, TRF>(k, ss->s[0], mask_after_a, w, L);
-            if (rc) return rc;
-            HIPCHK(hipEventRecord(ss->ev[31], ss->s[0]));
-            k.mask_ready = ss->ev[31];
-        }
+    if constexpr (S::kMaskTable) {
+        if (table_after_a)
+            if (const int rc = fork_mask_table<S>(k, st, ss, mask_row, w, L)) return rc;
     }
+
     tk_begin(TK_ROW, st);
-    if constexpr (N2 > 8192) {
-        // 16384-point rows (C5's 1024 x 16384 split): one row at a time
-        // (PairRowsSeq); no transfer function / tail variant (run_fourstep
-        // keeps those runs on the 2048 x 8192 split)
-        if (k.p.htab || k.p.tail_a) return fail(PSS_EUNSUPPORTED, "%d-point rows: no transfer function", N2);
-        // (16 values of each row per thread: 512 threads with 32 measured
-        // 47.8 against 43.9 ms at C5, profiles/r05/r16/)
-        constexpr int TS = N2 / 16;
-        using PRS = PairRowsSeq<N2, TS, RF, RI>;
-        k_pair_row_seq<PRS, TS, false><<<dim3((unsigned)k.npairs, (unsigned)(N1 / 2 - 1)), dim3(TS), 0, st>>>(k);
-        k_pair_row_seq<PRS, TS, true><<<dim3((unsigned)k.npairs, 1u), dim3(TS), 0, st>>>(k);
+    const dim3 gr((unsigned)k.npairs, (unsigned)(N1 / 2));
+    const bool plain = !k.p.htab && !k.p.tail_a;
+    if (N2 > 8192 || (N2 == 8192 && plain)) {
+        // one row at a time (PairRowsSeq): the plain runs on 8192-point rows,
+        // and the 16384-point rows (C5's 1024 x 16384 split), which have no
+        // transfer function / tail variant (run_fourstep keeps those runs on
+        // the 2048 x 8192 split)
+        if (!plain) return fail(PSS_EUNSUPPORTED, "%d-point rows: no transfer function", N2);
+        if constexpr (N2 >= 8192) {
+            using PRS = typename S::PRS;
+            constexpr int TS = S::TS;
+            k_pair_row_seq<PRS, TS, false><<<dim3(gr.x, gr.y - 1), dim3(TS), 0, st>>>(k);
+            k_pair_row_seq<PRS, TS, true><<<dim3(gr.x, 1u), dim3(TS), 0, st>>>(k);
+        }
         plan_note(" R:pair_row_seq");
     } else if (k.p.htab) {
-        k_pair_row<PR, TR, false, true><<<dim3((unsigned)k.npairs, (unsigned)(N1 / 2)), dim3(TR), 0, st>>>(k);
+        if constexpr (N2 <= 8192) k_pair_row<PR, TR, false, true><<<gr, dim3(TR), 0, st>>>(k);
         plan_note(" R:pair_row_htab");
     } else if (k.p.tail_a) {
-        k_pair_row<PR, TR, true><<<dim3((unsigned)k.npairs, (unsigned)(N1 / 2)), dim3(TR), 0, st>>>(k);
+        if constexpr (N2 <= 8192) k_pair_row<PR, TR, true><<<gr, dim3(TR), 0, st>>>(k);
         plan_note(" R:pair_row_tail");
-    } else if constexpr (N2 == 8192) {
-        constexpr int TS = N2 / 16;                  // 16 values of each row per thread
-        using PRS = PairRowsSeq<N2, TS, RF, RI>;
-        k_pair_row_seq<PRS, TS, false><<<dim3((unsigned)k.npairs, (unsigned)(N1 / 2 - 1)), dim3(TS), 0, st>>>(k);
-        k_pair_row_seq<PRS, TS, true><<<dim3((unsigned)k.npairs, 1u), dim3(TS), 0, st>>>(k);
-        plan_note(" R:pair_row_seq");
     } else {
-        k_pair_row<PR, TR><<<dim3((unsigned)k.npairs, (unsigned)(N1 / 2)), dim3(TR), 0, st>>>(k);
+        if constexpr (N2 < 8192) k_pair_row<PR, TR><<<gr, dim3(TR), 0, st>>>(k);
         plan_note(" R:pair_row");
     }
     tk_end(st);
     LAUNCHCHK();
-    const bool fast = PCC::kItemsExact && fast_epilogue(k);
+
+    const bool fast = PC::kItemsExact && fast_epilogue(k);
     // the generic pass C reads the null decisions as bits
     if (k.mask_ready && !fast) HIPCHK(hipStreamWaitEvent(st, k.mask_ready, 0));
     tk_begin(TK_COLC, st);
     if (fast) {
-        if constexpr (PCC::kItemsExact) {
-            if constexpr (N1 == 2048 && N2 % 16 == 0) {
-                k_pairC_fast32<PairCols<N1, 16, 512, CF, CI, -1>, 512>
-                    <<<dim3((unsigned)(N2 / 16), (unsigned)k.npairs), dim3(512), 0, st>>>(k);
-                plan_note(" C:fast32");
-            } else if constexpr (N1 == 1024 && N2 % 16 == 0) {
-                k_pairC_fast32<PairCols<N1, 16, 512, CF, CI, -1>, 512, 4>
-                    <<<dim3((unsigned)(N2 / 16), (unsigned)k.npairs), dim3(512), 0, st>>>(k);
-                plan_note(" C:fast C:cols16x2");
-            } else {
-                k_pairC_fast<PCC, TC><<<dim3((unsigned)(N2 / BC), (unsigned)k.npairs), dim3(TC), 0, st>>>(k);
-                plan_note(" C:fast");
-            }
+        const dim3 g16((unsigned)(N2 / 16), (unsigned)k.npairs);
+        if constexpr (N1 == 2048) {
+            k_pairC_fast32<typename S::PCFast32, 512><<<g16, dim3(512), 0, st>>>(k);
+            plan_note(" C:fast32");
+        } else if constexpr (N1 == 1024) {
+            k_pairC_fast32<typename S::PCFast32, 512, 4><<<g16, dim3(512), 0, st>>>(k);
+            plan_note(" C:fast C:cols16x2");
+        } else if constexpr (PC::kItemsExact) {
+            k_pairC_fast<typename S::PCFast, T><<<gc, dim3(T), 0, st>>>(k);
+            plan_note(" C:fast");
         }
     } else if (PC::kRegCols && fold_epilogue(k)) {
         if constexpr (PC::kRegCols) {
-            // 128 columns per workgroup: the lane-private LDS staging of the
-            // column (N1 x 8 B per lane) then allows ~5 workgroups per CU
-            constexpr int FB = B > 128 ? 128 : B;
-            using PCF = PairCols<N1, FB, FB, CF, CI>;
-            k_pairC_fold<PCF, FB><<<dim3((unsigned)(N2 / FB), (unsigned)k.npairs), dim3(FB), 0, st>>>(k);
-            plan_note(" C:fold");
+            constexpr int FB = S::FB;
+            k_pairC_fold<typename S::PCFold, FB><<<dim3((unsigned)(N2 / FB), gc.y), dim3(FB), 0, st>>>(k);
         }
+        plan_note(" C:fold");
     } else {
         k_pairC<PC, T><<<gc, dim3(T), 0, st>>>(k);
         plan_note(" C:generic");
     }
     tk_end(st);
     LAUNCHCHK();
+
     if (fast && k.mtab) {
         if (k.mask_ready) HIPCHK(hipStreamWaitEvent(st, k.mask_ready, 0));
-        const int rc = launch_null_fix(k, st);
-        if (rc) return rc;
+        if (const int rc = launch_null_fix(k, st)) return rc;
         plan_note(" N:fix_list");
     }
     return PSS_OK;
 }
 
 // Mixed-radix four-step (see smooth_split): columns of N1 in registers (one
-// column per thread, B = T columns per workgroup), rows by the power-of-two
-// row engine.  Generic (looped) column kernels; no mask table.
+// column per thread, B = T columns per workgroup) on the row engine of k.N2.
+// Generic (looped) column kernels; no mask table.
 template <int N1, typename CF, typename CI, int T>
 static int launch_smooth_n2(KP &k, hipStream_t st) {
+    using C = RegCols<N1, CF, CI, T>;
     switch (k.N2) {
-        case 1024: return launch_pair<N1, T, T, CF, CI, 1024, 128, C1kF, C1kI, 64>(k, st, nullptr);
-        case 2048: return launch_pair<N1, T, T, CF, CI, 2048, 256, C2kF, C2kI, 128>(k, st, nullptr);
-        case 4096: return launch_pair<N1, T, T, CF, CI, 4096, 512, C4k, C4k, 256>(k, st, nullptr);
-        case 8192: return launch_pair<N1, T, T, CF, CI, 8192, 1024, C8kF, C8kI, 512>(k, st, nullptr);
+        case 1024: return launch_pair<Split<C, RowsOf<1024>>>(k, st, nullptr);
+        case 2048: return launch_pair<Split<C, RowsOf<2048>>>(k, st, nullptr);
+        case 4096: return launch_pair<Split<C, RowsOf<4096>>>(k, st, nullptr);
+        case 8192: return launch_pair<Split<C, RowsOf<8192>>>(k, st, nullptr);
         default: return fail(PSS_EUNSUPPORTED, "mixed-radix four-step: N2=%lld", (long long)k.N2);
     }
 }

@@ -87,6 +87,19 @@ def test_search_fast_bitwise_equals_generic(N, hip_lib):
     _fast_vs_generic(lambda: _search_run(N, 3, null), 3, N, g.tokens + (("N:table",) if null else ()), fast)
 
 
+def test_search_fast_mask_table_forked_before_pass_a(hip_lib):
+    """The delayed null's mask table forked onto the side stream BEFORE pass A
+    (more channels than kMaskAfterANchan = 1024 of csrc/pss_fourstep.hpp; the
+    3-channel cases above fork after pass A): the fast run waits for the table
+    before the fix-up, the generic run before pass C.  The smallest four-step
+    length (16 x 1024) at the smallest even channel count above the threshold."""
+    N, nchan = 1 << 14, 1026            # kMaskAfterANchan + 2 (not readable from the library)
+    g = G.of_length(N, 1)
+    assert g.search_fast, g
+    fast = G.fast_tokens(g, shared_profile=True) + ("N:fix_list",)
+    _fast_vs_generic(lambda: _search_run(N, nchan, True), nchan, N, g.tokens + ("N:table",), fast)
+
+
 # ---------------------------------------------------------------------------
 # (c) fold-mode fast passes == generic
 # ---------------------------------------------------------------------------
