@@ -220,7 +220,10 @@ int pss_last_error(char *buf, size_t n);
  * R:<row pass> C:<pass C> N:<null>", e.g. "2048x4194304: fourstep 1024x4096
  * A:fast R:pair_row C:fast N:table N:fix_list" -- copied into buf (up to n - 1
  * bytes, NUL-terminated); returns the log's length and clears it.  The parity
- * tests assert with it which kernels produced the bits they check.        */
+ * tests assert with it which kernels produced the bits they check.  "C:null"
+ * (after "C:fast C:cols16x2", a delayed null on 1024-point columns): pass C
+ * nulled the samples the mask table nulls for every fractional shift itself,
+ * and "N:fix_list" then rewrites only the f-dependent hits.                */
 int pss_plan_collect(char *buf, size_t n);
 
 /* Opt-in kernel timing for benchmarks: while enabled, pss_run records a pair

@@ -48,21 +48,29 @@ __global__ __launch_bounds__(256) void k_mask_bits(KP k, uint32_t *bm) {
 
 // Table words (32 positions each) that hold a position nulled for some f:
 // the only words the null fix-up has to visit (the nulled pulses and their
-// Gibbs ringing, ~10-20% of the row).  Compacted once per run.
+// Gibbs ringing, ~10-20% of the row).  Compacted once per run.  A second
+// list holds the words with a position whose decision depends on f (the box
+// edges, ~1 % of positions): all the fix-up visits after a pass C that nulled
+// the always-nulled samples itself.
 __global__ __launch_bounds__(256) void k_mask_words(const uint2 *bits, uint32_t nwords, uint32_t *list,
-                                                    uint32_t *count) {
+                                                    uint32_t *count, uint32_t *list_f, uint32_t *count_f) {
     const uint32_t w = blockIdx.x * 256u + threadIdx.x;
-    bool nz = false;
+    bool nz = false, fd = false;
     if (w < nwords) {
         const uint2 b = bits[w];
         nz = (b.x | b.y) != 0u;
+        fd = b.y != 0u;
     }
-    const uint64_t bal = __ballot(nz);
+    const uint64_t bal = __ballot(nz), balf = __ballot(fd);
     const int lane = threadIdx.x & 63;
-    uint32_t b0 = 0;
+    const uint64_t below = (1ull << lane) - 1ull;
+    uint32_t b0 = 0, f0 = 0;
     if (lane == 0 && bal) b0 = atomicAdd(count, (uint32_t)__popcll(bal));
+    if (lane == 0 && balf) f0 = atomicAdd(count_f, (uint32_t)__popcll(balf));
     b0 = __shfl(b0, 0);
-    if (nz) list[b0 + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] = w;
+    f0 = __shfl(f0, 0);
+    if (nz) list[b0 + (uint32_t)__popcll(bal & below)] = w;
+    if (fd) list_f[f0 + (uint32_t)__popcll(balf & below)] = w;
 }
 
 // Delayed null fix-up driven by the word list: item (channel r, listed table
@@ -73,7 +81,12 @@ __global__ __launch_bounds__(256) void k_mask_words(const uint2 *bits, uint32_t 
 // belongs to exactly one item, so items write disjoint samples; 4-sample
 // groups cut by an unaligned window are drawn by both neighbours, each
 // writing its own samples.  Grid-stride over the list (its length is only
-// known on the device).
+// known on the device).  FDEP: after a pass C that nulled the always-nulled
+// samples (PairCols::passC_fast32<true>) -- k.wlist is then the list of
+// f-dependent words (launch_pair), and only the hits at f-dependent positions
+// are written (the two sets are disjoint: one writer per sample in either
+// kernel).
+template <bool FDEP>
 __global__ __launch_bounds__(256) void k_null_fix_list(KP k) {
     __shared__ uint32_t desc[4][64 * 9];
     __shared__ uint32_t dbase[4][64 * 9];
@@ -96,6 +109,7 @@ __global__ __launch_bounds__(256) void k_null_fix_list(KP k) {
             const uint32_t w = k.wlist[i];
             n0 = ((w << 5) + is) & nm;                   // data sample of table position 32 w
             hits = mask_run(k, n0, is, t, 32u);
+            if (FDEP) hits &= k.mt_bits[w].y;            // (the window is word w itself)
         }
         if (__ballot(hits != 0u) == 0ull) continue;
         // (group, 4-bit mask) entries of this lane: samples n0 + j in groups
@@ -316,8 +330,9 @@ int launch_mask_table(const float *nodes, int64_t N, uint2 *bits, uint32_t *base
     LAUNCHCHK();
     return PSS_OK;
 }
-int launch_mask_words(const uint2 *bits, uint32_t nwords, uint32_t *list, uint32_t *count, hipStream_t st) {
-    k_mask_words<<<dim3((nwords + 255) / 256), dim3(256), 0, st>>>(bits, nwords, list, count);
+int launch_mask_words(const uint2 *bits, uint32_t nwords, uint32_t *list, uint32_t *count, uint32_t *list_f,
+                      uint32_t *count_f, hipStream_t st) {
+    k_mask_words<<<dim3((nwords + 255) / 256), dim3(256), 0, st>>>(bits, nwords, list, count, list_f, count_f);
     LAUNCHCHK();
     return PSS_OK;
 }
@@ -326,11 +341,14 @@ int launch_mask_bits(const KP &k, uint32_t *bm, hipStream_t st) {
     LAUNCHCHK();
     return PSS_OK;
 }
-int launch_null_fix(const KP &k, hipStream_t st) {
+int launch_null_fix(const KP &k, hipStream_t st, bool fdep) {
     tk_begin(TK_NULLFIX, st);
-    // grid-stride over the word list: ~1/8 of the words per channel
-    const unsigned gx = (unsigned)((k.N / 32 / 8 + 255) / 256);
-    k_null_fix_list<<<dim3(gx ? gx : 1, (unsigned)k.p.nchan), dim3(256), 0, st>>>(k);
+    // grid-stride over the word list: ~1/8 of the words per channel (the
+    // f-dependent words: ~1/64)
+    const unsigned gx = (unsigned)((k.N / 32 / (fdep ? 64 : 8) + 255) / 256);
+    const dim3 g(gx ? gx : 1, (unsigned)k.p.nchan);
+    if (fdep) k_null_fix_list<true><<<g, dim3(256), 0, st>>>(k);
+    else k_null_fix_list<false><<<g, dim3(256), 0, st>>>(k);
     tk_end(st);
     LAUNCHCHK();
     return PSS_OK;

@@ -20,7 +20,10 @@
 //     Shorter columns (2^14 .. 2^21) and the mixed-radix splits: passC_fast,
 //     the block in LDS, on pass A's block width ("C:fast");
 //   * the delayed-null mask table built on a side stream next to pass A, and
-//     applied by the compacted fix-up (k_null_fix_list) after pass C.
+//     applied by the compacted fix-up (k_null_fix_list) after pass C; on
+//     1024-point columns pass C itself nulls the samples the table nulls for
+//     every f, in its staging ("C:null"), and the fix-up visits only the
+//     words with an f-dependent position.
 
 // ---------------------------------------------------------------------------
 // path 2: four-step, N = N1 * N2, sample n = N2*n1 + n2, bin k = k1 + N1*k2.
@@ -1184,6 +1187,25 @@ struct PairCols<N1, B, T, RList<F...>, RList<I...>, XRS> {
     //     128-VGPR cap: 94 used, no scratch), so two workgroups share a CU and
     //     one loads or stores while the other transforms.
     // Bitwise the values of passC_fast (same twiddles, FFT and epilogue).
+    //
+    // NULLC (1024-point columns with the mask table; plan token C:null): the
+    // samples the table nulls for EVERY f are nulled here, in the staging,
+    // instead of being stored and then rewritten by the fix-up.  Each thread
+    // takes the 16-bit window of the table's always bits (mt_bits[].x, no
+    // root records, no f-dependent branch) of its two rows' 16-sample
+    // segments, for both channels, at the start of the kernel; next to a
+    // channel's staging writes every non-zero nibble appends one 16-bit
+    // entry {n1:10, c4/4:2, nibble:4} to an LDS list (a ballot prefix and one
+    // LDS atomic per wave; the list holds the whole block, 4096 entries, so
+    // it cannot overflow).  After the staging barrier the list is
+    // walked densely -- the replacement draws cost what the nulled fraction
+    // costs, not one divergent branch per wave -- and overwrites the staged
+    // value with vr * sc; the store loop then adds the noise it draws anyway:
+    // fmaf(nn, vn, vr * sc), the fix-up's expression and bits.  Every sample
+    // is still stored, as whole 64-B segments.  The f-dependent positions
+    // (~1 %) are left to k_null_fix_list<true>.  80 136 B of LDS: two
+    // workgroups still share a CU.
+    template <bool NULLC = false>
     __device__ static void passC_fast32(const KP &k) {
         static_assert((N1 == 1024 || N1 == 2048) && (T == 1024 || T == 512) && B % (T / 64) == 0 &&
                       kWaveCols == false, "register-resident wide pass C: 2^m columns of 1024 / 2048");
@@ -1200,8 +1222,16 @@ struct PairCols<N1, B, T, RList<F...>, RList<I...>, XRS> {
         constexpr int BUF = (B1 > B2 ? B1 : B2) > B3 ? (B1 > B2 ? B1 : B2) : B3;
         __shared__ __align__(16) char smem[BUF];
         __shared__ cf tw16[kTw16Size];
+        static_assert(!NULLC || (N1 == 1024 && T == 512 && B == 16), "NULLC: two rows per thread, 16-bit entries");
+        // (NULLC only; unused and not allocated otherwise) the nulled items of
+        // the channel being staged, and their count per channel
+        __shared__ uint16_t nlist[NULLC ? N1 * B / 4 : 1];
+        __shared__ uint32_t ncount[2];
         const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
         tw16_fill(tw16, tid, T);
+        if constexpr (NULLC) {
+            if (tid < 2) ncount[tid] = 0u;              // (phase 1's barriers come before its first use)
+        }
         int cbx, pr;
         xcd_block(cbx, pr);
         const int ra = 2 * pr - k.poff, rb = ra + 1;
@@ -1214,6 +1244,34 @@ struct PairCols<N1, B, T, RList<F...>, RList<I...>, XRS> {
         const uint32_t RP = (uint32_t)rpitch(k);
         cf *hb = reinterpret_cast<cf *>(smem);
         cf v[CPW][E1];
+        // NULLC: the always bits of rows tid, tid + T of both channels --
+        // table positions p0 .. p0 + 15, p0 = (n1 N2 + n20 - is) mod N, in
+        // two table words (the second wraps with the table).  Loaded here,
+        // ahead of the spill rows, and packed into one register per channel
+        // after phase 1: loaded where phase 3 uses them, the ramp word and
+        // then the table words were two exposed latencies per channel.
+        uint32_t mlo[2][N1 / T] = {}, mhi[2][N1 / T] = {}, msh[2][N1 / T] = {}, nwin[2] = {0u, 0u};
+        if constexpr (NULLC) {
+#pragma unroll
+            for (int ch = 0; ch < 2; ++ch) {
+                if (ch ? hasb : hasa) {                 // (uniform; the edge pairs' missing channel has no ramp word)
+                    uint32_t is;
+                    float tf;
+                    mask_split((uint64_t)p.mask_ramp[ch ? rb : ra], k.log2n, is, tf);
+                    const uint32_t nm = (uint32_t)k.N - 1u, wm = nm >> 5;
+                    const uint32_t *ax = reinterpret_cast<const uint32_t *>(k.mt_bits);   // .x of word w: ax[2 w]
+#pragma unroll
+                    for (int j = 0; j < N1 / T; ++j) {
+                        const uint32_t p0 = ((uint32_t)(tid + j * T) * (uint32_t)N2 + (uint32_t)n20 - is) & nm;
+                        const uint32_t w = p0 >> 5;
+                        PSS_DASSERT(w <= wm);
+                        mlo[ch][j] = ax[2u * w];
+                        mhi[ch][j] = ax[2u * ((w + 1u) & wm)];
+                        msh[ch][j] = p0 & 31u;
+                    }
+                }
+            }
+        }
         // The 1024-point form runs at the 128-VGPR cap (two workgroups per
         // CU) with 64 VGPRs of columns: each phase takes its thread indices
         // through opaque(), so that address arithmetic of a later phase (or of
@@ -1258,6 +1316,14 @@ struct PairCols<N1, B, T, RList<F...>, RList<I...>, XRS> {
             }
         }
         __syncthreads();
+        if constexpr (NULLC) {
+#pragma unroll
+            for (int ch = 0; ch < 2; ++ch)
+#pragma unroll
+                for (int j = 0; j < N1 / T; ++j)
+                    nwin[ch] |= ((uint32_t)(((((uint64_t)mhi[ch][j]) << 32) | mlo[ch][j]) >> msh[ch][j]) & 0xffffu)
+                                << (16 * j);
+        }
         // (2) the inverse column FFTs through the wave's own LDS row
         {
             cf *wl = reinterpret_cast<cf *>(smem) + wv * LW::RS;
@@ -1284,10 +1350,65 @@ struct PairCols<N1, B, T, RList<F...>, RList<I...>, XRS> {
 #pragma unroll
                 for (int c = 0; c < CPW; ++c) stg[pos * OSP + wv + NW * c] = (ch ? v[c][i].y : v[c][i].x) * invN;
             }
+            if constexpr (NULLC) {
+                if (ch ? hasb : hasa) {
+                    // entries of this thread (at most 2 x 4), compacted over the
+                    // wave: the exclusive prefix of the counts from four ballots
+                    uint32_t win[N1 / T], cnt = 0;
+#pragma unroll
+                    for (int j = 0; j < N1 / T; ++j) {
+                        win[j] = (nwin[ch] >> (16 * j)) & 0xffffu;
+#pragma unroll
+                        for (int g = 0; g < 4; ++g) cnt += ((win[j] >> (4 * g)) & 15u) ? 1u : 0u;
+                    }
+                    const uint64_t below = (1ull << lane) - 1ull;
+                    uint32_t e = 0, total = 0;
+#pragma unroll
+                    for (int bit = 0; bit < 4; ++bit) {
+                        const uint64_t bal = __ballot((cnt >> bit) & 1u);
+                        e += (uint32_t)__popcll(bal & below) << bit;
+                        total += (uint32_t)__popcll(bal) << bit;
+                    }
+                    uint32_t b0 = 0;
+                    if (lane == 0 && total) b0 = atomicAdd(&ncount[ch], total);
+                    e += (uint32_t)__shfl((int)b0, 0);
+                    const uint32_t r0 = (uint32_t)fresh(tid);
+#pragma unroll
+                    for (int j = 0; j < N1 / T; ++j) {
+#pragma unroll
+                        for (int g = 0; g < 4; ++g) {
+                            const uint32_t h = (win[j] >> (4 * g)) & 15u;
+                            if (h) {
+                                PSS_DASSERT(e < (uint32_t)(N1 * B / 4));
+                                nlist[e++] = (uint16_t)(((r0 + (uint32_t)(j * T)) << 6) | ((uint32_t)g << 4) | h);
+                            }
+                        }
+                    }
+                }
+            }
             __syncthreads();
             const bool has = ch ? hasb : hasa;
             if (!has) continue;                         // (uniform)
             const uint32_t c = ch ? cb : ca;
+            if constexpr (NULLC) {
+                // the listed items, densely: replacement draws of the set bits
+                // over the staged values (disjoint items: any order)
+                const uint32_t ne = ncount[ch];
+                const Rng gr(p.seed, p.call_null, P_REP);
+                const float sc = p.null_rep_scale;
+                for (uint32_t e = (uint32_t)fresh(tid); e < ne; e += (uint32_t)T) {
+                    const uint32_t d = nlist[e], n1 = d >> 6, c4 = ((d >> 4) & 3u) * 4u;
+                    const uint32_t nb = n1 * (uint32_t)N2 + (uint32_t)n20 + c4;
+                    PSS_DASSERT(n1 < (uint32_t)N1 && (int64_t)nb + 4 <= k.N);
+                    const float4 xr = chi2_1x4(gr.bits(nb >> 2, c, 0u));
+                    float *sr = stg + n1 * OSP + c4;
+                    if (d & 1u) sr[0] = xr.x * sc;
+                    if (d & 2u) sr[1] = xr.y * sc;
+                    if (d & 4u) sr[2] = xr.z * sc;
+                    if (d & 8u) sr[3] = xr.w * sc;
+                }
+                __syncthreads();
+            }
             const Buf o(p.data + (int64_t)(ch ? rb : ra) * p.ld, rbytes);
             const int t0 = fresh(tid);
 #pragma unroll
@@ -1410,6 +1531,9 @@ __global__ __launch_bounds__(T) void k_pairC_fast(KP k) { C::passC_fast(k); }
 // columns, whose 72 KB of LDS then lets two workgroups share a CU.
 template <typename C, int T, int W = (T == 512 ? 2 : 4)>
 __global__ __launch_bounds__(T, W) void k_pairC_fast32(KP k) { C::passC_fast32(k); }
+// the 1024-point form that also nulls the always-nulled samples (NULLC)
+template <typename C>
+__global__ __launch_bounds__(512, 4) void k_pairC_null(KP k) { C::template passC_fast32<true>(k); }
 template <typename C, int T>
 __global__ __launch_bounds__(T) void k_node_col(KP k, float *nodes) { C::node_col(k, nodes); }
 // (4 waves per SIMD for columns up to 30: the compiler would otherwise keep
@@ -1558,9 +1682,12 @@ static inline int build_mask_table(KP &k, hipStream_t st, const float *mask_row,
     {
         uint32_t *wl = reinterpret_cast<uint32_t *>(w + L.wlist);
         uint32_t *wcount = reinterpret_cast<uint32_t *>(w + L.misc + 8);
-        HIPCHK(hipMemsetAsync(wcount, 0, 4, st));
         const uint32_t nwords = (uint32_t)(k.N / 32);
-        if (const int rc = launch_mask_words(k.mt_bits, nwords, wl, wcount, st)) return rc;
+        // (the f-dependent words' list and count: WsLayout::wlist_f)
+        uint32_t *wlf = reinterpret_cast<uint32_t *>(w + L.wlist_f);
+        uint32_t *wcount_f = reinterpret_cast<uint32_t *>(w + L.wcount_f);
+        HIPCHK(hipMemsetAsync(wcount, 0, 8, st));           // both counts (misc + 8, misc + 12)
+        if (const int rc = launch_mask_words(k.mt_bits, nwords, wl, wcount, wlf, wcount_f, st)) return rc;
         k.wlist = wl;
         k.nwlist = wcount;
     }
@@ -1716,8 +1843,13 @@ static int launch_pair(KP &k, hipStream_t st, const float *mask_row) {
     LAUNCHCHK();
 
     const bool fast = PC::kItemsExact && fast_epilogue(k);
-    // the generic pass C reads the null decisions as bits
-    if (k.mask_ready && !fast) HIPCHK(hipStreamWaitEvent(st, k.mask_ready, 0));
+    // the fast pass C on 1024-point columns nulls the always-nulled samples
+    // itself (PairCols::passC_fast32<true>) and leaves the fix-up the
+    // f-dependent positions
+    const bool nullc = fast && N1 == 1024 && S::kMaskTable && k.mtab;
+    // the generic pass C reads the null decisions as bits, the nulling one
+    // the table's always bits (built beside pass A or the row pass: long done)
+    if (k.mask_ready && (!fast || nullc)) HIPCHK(hipStreamWaitEvent(st, k.mask_ready, 0));
     tk_begin(TK_COLC, st);
     if (fast) {
         const dim3 g16((unsigned)(N2 / 16), (unsigned)k.npairs);
@@ -1725,8 +1857,9 @@ static int launch_pair(KP &k, hipStream_t st, const float *mask_row) {
             k_pairC_fast32<typename S::PCFast32, 512><<<g16, dim3(512), 0, st>>>(k);
             plan_note(" C:fast32");
         } else if constexpr (N1 == 1024) {
-            k_pairC_fast32<typename S::PCFast32, 512, 4><<<g16, dim3(512), 0, st>>>(k);
-            plan_note(" C:fast C:cols16x2");
+            if (nullc) k_pairC_null<typename S::PCFast32><<<g16, dim3(512), 0, st>>>(k);
+            else k_pairC_fast32<typename S::PCFast32, 512, 4><<<g16, dim3(512), 0, st>>>(k);
+            plan_note(nullc ? " C:fast C:cols16x2 C:null" : " C:fast C:cols16x2");
         } else if constexpr (PC::kItemsExact) {
             k_pairC_fast<typename S::PCFast, T><<<gc, dim3(T), 0, st>>>(k);
             plan_note(" C:fast");
@@ -1745,8 +1878,13 @@ static int launch_pair(KP &k, hipStream_t st, const float *mask_row) {
     LAUNCHCHK();
 
     if (fast && k.mtab) {
-        if (k.mask_ready) HIPCHK(hipStreamWaitEvent(st, k.mask_ready, 0));
-        if (const int rc = launch_null_fix(k, st)) return rc;
+        if (k.mask_ready && !nullc) HIPCHK(hipStreamWaitEvent(st, k.mask_ready, 0));
+        KP kf = k;
+        if (nullc) {   // the f-dependent words' list in place of the full one
+            kf.wlist = reinterpret_cast<const uint32_t *>(w + L.wlist_f);
+            kf.nwlist = reinterpret_cast<const uint32_t *>(w + L.wcount_f);
+        }
+        if (const int rc = launch_null_fix(kf, st, nullc)) return rc;
         plan_note(" N:fix_list");
     }
     return PSS_OK;

@@ -27,7 +27,8 @@ enum { TK_ELEM = 0, TK_SINGLE, TK_COLA, TK_ROW, TK_COLC, TK_FALLBACK, TK_NULLFIX
 void tk_begin(int kind, hipStream_t st);
 void tk_end(hipStream_t st);
 // launch-plan log (pss_plan_collect): every launch path notes the kernels it
-// picked ("fourstep 1024x4096 A:fast R:pair_row C:fast N:fix_list"), so the
+// picked ("fourstep 1024x4096 A:fast R:pair_row C:fast N:fix_list"; C:null: the
+// fast pass C nulled the always-nulled samples, N:fix_list the rest), so the
 // parity tests can assert which kernels produced the bits they check
 void plan_note(const char *fmt, ...);
 
@@ -213,6 +214,12 @@ struct WsLayout {
     int64_t rf_tw, rf_B, rf_mx;        // float64 null decisions: e^{2 pi i n/N} [N], B [N/2+1] (double2), row max [nchan]
     int64_t rf_part, rf_list, rf_cnt;  // ... partial spectra [kBsParts][N/2+1] (double2), candidate list, its count
     int64_t pcol;                      // four-step: the profile at every sample (float4 items, k_prof_cols)
+    // four-step: the table words with an f-dependent position (k_mask_words'
+    // second list: the fix-up after a pass C that nulled the always-nulled
+    // samples) and its count.  The list takes the node rows' bytes -- their
+    // last reader, k_mask_table, is ahead of k_mask_words on its stream -- and
+    // the count a word of misc, so the workspace keeps its size.
+    int64_t wlist_f, wcount_f;
 };
 
 static inline WsLayout ws_layout(int32_t nchan, int64_t N, bool filt = false) {
@@ -240,6 +247,8 @@ static inline WsLayout ws_layout(int32_t nchan, int64_t N, bool filt = false) {
         w.base = o;  o += al256((N / 32) * 4);
         w.coef = o;  o += al256(N * KREC * 4);
         w.misc = o;  o += 256;
+        w.wlist_f = w.nodes;
+        w.wcount_f = w.misc + 12;                              // (misc + 8: the full list's count)
         w.mbits = o; o += al256((int64_t)nchan * (N / 8));   // per-channel null bits
         w.rtab = o;  o += al256(npairs * 2 * 64 * 8);          // row-pass pair ramp factors (RFL <= 64)
         w.wlist = o; o += al256((N / 32) * 4);                 // null fix-up: table words with nulls
@@ -330,7 +339,8 @@ static inline bool fast_epilogue(const KP &k) {
 // ---------------------------------------------------------------------------
 int launch_elementwise(const KP &k, hipStream_t st);              // pss_pipeline.hip
 int launch_box_row(const KP &k, float *row, hipStream_t st);      // pss_pipeline.hip
-int launch_null_fix(const KP &k, hipStream_t st);                 // pss_fourstep.hip
+// (fdep: pass C nulled the always-nulled samples; only the f-dependent hits are left)
+int launch_null_fix(const KP &k, hipStream_t st, bool fdep);      // pss_fourstep.hip
 int run_fourstep(KP &k, hipStream_t st, const float *mask_row);   // pss_fourstep.hip
 int run_smooth(KP &k, hipStream_t st);                            // pss_smooth.hip (N1 = 6 .. 20)
 int run_smooth_b(KP &k, hipStream_t st);                          // pss_smooth_b.hip (N1 = 24, 30, 40)
@@ -347,5 +357,6 @@ int shift_rows_odd(float *rows, int32_t nrows, int64_t n, int64_t ld, const uint
 int launch_node_params(uint64_t *ramp, float *nyq, int L, hipStream_t st);
 int launch_mask_table(const float *nodes, int64_t N, uint2 *bits, uint32_t *base, float *coef, uint32_t *counter,
                       hipStream_t st);
-int launch_mask_words(const uint2 *bits, uint32_t nwords, uint32_t *list, uint32_t *count, hipStream_t st);
+int launch_mask_words(const uint2 *bits, uint32_t nwords, uint32_t *list, uint32_t *count, uint32_t *list_f,
+                      uint32_t *count_f, hipStream_t st);
 int launch_mask_bits(const KP &k, uint32_t *bm, hipStream_t st);

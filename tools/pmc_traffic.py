@@ -18,7 +18,7 @@ from collections import defaultdict
 # times the generic kernels (k_pairA / k_pairC, with the mask-bit pass), whose
 # traffic must not be averaged into the bench line's
 KIND = {"k_pairA_fast": "fourstep_colA", "k_pair_row": "fourstep_row",
-        "k_pairC_fast": "fourstep_colC", "k_pairC_fast32": "fourstep_colC",
+        "k_pairC_fast": "fourstep_colC", "k_pairC_fast32": "fourstep_colC", "k_pairC_null": "fourstep_colC",
         "k_null_fix_list": "null_fix"}
 
 

@@ -16,7 +16,7 @@ import sys
 from collections import defaultdict
 
 KIND = {"k_pairA_fast": "fourstep_colA", "k_pair_row": "fourstep_row",
-        "k_pairC_fast": "fourstep_colC", "k_pairC_fast32": "fourstep_colC",
+        "k_pairC_fast": "fourstep_colC", "k_pairC_fast32": "fourstep_colC", "k_pairC_null": "fourstep_colC",
         "k_null_fix_list": "null_fix"}
 
 
