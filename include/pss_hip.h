@@ -642,6 +642,94 @@ int pss_accel_resample(const float *x, int32_t nser, int64_t T, int64_t ld, cons
                        const int64_t *kappa, const float *sub, int32_t nrows, int64_t n_out, float *out,
                        int64_t out_ld, void *stream);
 
+/*
+ * Fast folding search of a DM-time plane (extension, no reference
+ * counterpart), three entry points: the time scrunch, the folding transform
+ * and the search of its profiles.  Common to all three: all arithmetic on data
+ * is IEEE float32, every line one rounded operation, no fused multiply-add;
+ * all index arithmetic is integer (64-bit wherever a product can pass 2^31);
+ * no atomics, no allocation inside the library, no table from the caller.
+ *
+ * pss_ffa_scrunch: x[nser][ld] float32 holds T samples per row, sub[nser] is a
+ * device array or NULL.  The scrunch by 2^lf is a pairwise tree:
+ *   y_0[t]        = x[i * ld + t] - sub[i]        (sub == NULL: the bits are copied)
+ *   y_{k+1}[u]    = y_k[2u] + y_k[2u + 1]
+ *   y[i * y_ld + u] = y_lf[u]                     u < n = T >> lf
+ * Samples at and beyond n << lf are not read; nothing is written outside
+ * y[i * y_ld + 0 .. n).  Scrunching octave o + 1 from octave o (lf = 1, sub
+ * NULL) gives the bits of scrunching from the raw series: the tree is the same.
+ * PSS_EINVAL (nothing launched) on a NULL x / y, nser < 1, lf outside [0, 16],
+ * T < 1 or T >> lf < 1, ld < T, y_ld < n, and when ceil(n / 256) * nser
+ * exceeds 2^31 - 1 (the launch grid).
+ */
+int pss_ffa_scrunch(const float *x, int32_t nser, int64_t T, int64_t ld, const float *sub, int32_t lf, float *y,
+                    int64_t y_ld, void *stream);
+
+/*
+ * pss_ffa_transform: y[nser][ld] float32 holds n samples per row.  For series
+ * i, base period p = p0 + pi (pi < np) and m = floor(n / p), the leaves are the
+ * rows R_r[f] = y[i * ld + r * p + f], r < m, f < p, and the m output profiles
+ * F(0, m) come from a top-down halving recursion:
+ *   F(a, 1)_0 = R_a
+ *   F(a, m), m >= 2:  h = m / 2 (rounded down), t = m - h, H = F(a, h),
+ *                     Tl = F(a + h, t); for s < m:
+ *     i_s = floor((2 s (h - 1) + (m - 1)) / (2 (m - 1)))
+ *     j_s = floor((2 s (t - 1) + (m - 1)) / (2 (m - 1)))
+ *     b_s = floor((2 s h       + (m - 1)) / (2 (m - 1)))
+ *     F_s[f] = H_{i_s}[f] + Tl_{j_s}[(f + b_s) mod p]           one float32 add
+ *   out[((i * np + pi) * n) + s * p + f] = F(0, m)_s[f]
+ * Profile s is the fold at the period p + s / (m - 1) samples (m = 1: the
+ * series itself).  Words [m p, n) of each block of n are not written and
+ * samples [m p, n) of a series are not read.  The tree is part of the
+ * contract: the bits depend on neither the tiling, the number of levels a
+ * workgroup computes in LDS, the alignment of y / ld / out nor the other
+ * periods and series of the call.  Different p of one call can have trees of
+ * different depth; a node of one row at an inner level is a copy.  (i_s, j_s,
+ * b_s) and a row's node are found by descending the tree per output row, at
+ * most 27 uniform integer steps against p adds.
+ * work is a second buffer of nser * np * n floats: the levels ping-pong
+ * between the two.  It holds nothing of use afterwards and must not overlap
+ * out.  The subtree below the first depth whose nodes hold at most 8192
+ * floats is computed by one workgroup in LDS in one pass over the block; the
+ * levels above it take one pass each.
+ * PSS_EINVAL (nothing launched) on a NULL pointer, nser < 1, p0 < 2, np < 1,
+ * p0 + np - 1 > min(n, 4096), n > 2^28, ld < n, and when a launch grid
+ * (ceil(floor(n / p0) / 4) * nser * np workgroups a level) exceeds 2^31 - 1.
+ */
+int pss_ffa_transform(const float *y, int32_t nser, int64_t n, int64_t ld, int32_t p0, int32_t np, float *out,
+                      float *work, void *stream);
+
+/*
+ * pss_ffa_profile_search: a circular boxcar matched filter over the profiles
+ * of pss_ffa_transform, taken in its layout (prof = its out, the same nser, n,
+ * p0, np), reduced to cells of `cell` consecutive shifts s.  rstd[nser] and
+ * rm[np] are device arrays.  With m = floor(n / p) and prof_s the profile s of
+ * block (i, pi):
+ *   S_0[f]     = prof_s[f]
+ *   S_{k+1}[f] = S_k[f] + S_k[(f + 2^k) mod p]
+ *   valid (k, f): k < nw, 2^(k+1) <= p, f < p
+ *   g          = rstd[i] * rm[pi]                               one rounded product
+ *   z_k[f]     = (S_k[f] * a_k) * g       a_k as in pss_boxcar_search
+ *   cell q < nq_p = ceil(m / cell): the lexicographic maximum of (z, -k, -s, -f)
+ *                over q * cell <= s < min((q + 1) * cell, m): the largest z; ties
+ *                go to the narrower width, then to the lower shift, then to the
+ *                lower phase; a NaN z never wins
+ *   snr  [(i * np + pi) * out_ld + q] = that z, -inf if nothing beat -inf
+ *   code [...] = (k << 16) | (s - q * cell)     (0 with -inf)
+ *   phase[...] = f                              (0 with -inf)
+ *   cells nq_p <= q < nq = ceil(floor(n / p0) / cell) hold -inf, 0, 0
+ * Nothing is written at or beyond column nq of a row.  With rm = 1 / sqrt(m)
+ * and rstd = 1 / sigma of a sample of the series, z is the box sum in units of
+ * its own standard deviation on white noise.
+ * PSS_EINVAL (nothing launched) on a NULL pointer, nser < 1, p0 < 2, np < 1,
+ * p0 + np - 1 > min(n, 4096), n > 2^28, nw outside [1, 11], cell not a power
+ * of two in [16, 2048], out_ld < nq, and when nq * nser * np exceeds 2^31 - 1
+ * (the launch grid).
+ */
+int pss_ffa_profile_search(const float *prof, int32_t nser, int64_t n, int32_t p0, int32_t np, const float *rstd,
+                           const float *rm, int32_t nw, int32_t cell, float *snr, int32_t *code, int32_t *phase,
+                           int64_t out_ld, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
