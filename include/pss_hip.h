@@ -431,6 +431,43 @@ int pss_dedisperse(const float *data, int32_t nchan, int64_t n, int64_t ld, cons
                    int32_t ndm, int32_t max_delay, float *out, int64_t out_ld, void *stream);
 
 /*
+ * Banded dedispersion from several source planes (extension, no reference
+ * counterpart): pss_dedisperse's direct sum taken over bands of `band`
+ * neighbouring channels, each trial reading the plane of its source -- both
+ * stages of the two-stage sub-band dedispersion are calls of it.
+ * data holds nsrc planes [nchan][ld] float32 (n samples per row), src_stride
+ * floats apart; delays[ndm][nchan] is a device table of int32 sample delays.
+ * With nb = ceil(nchan / band) bands (the last may be short), T = n -
+ * max_delay and q(j) = min(j / per_src, nsrc - 1) the source of trial j:
+ *   d(j, c) = min(max(delays[j * nchan + c], 0), max_delay)
+ *   out[(j * nb + s) * out_ld + t]
+ *           = sum_{c = s band .. min(nchan, (s + 1) band) - 1}
+ *                 data[q(j) * src_stride + c * ld + t + d(j, c)],   t < T, j < ndm, s < nb
+ * out is [ndm][nb][out_ld].  Stage 1 of the sub-band scheme is nsrc = 1,
+ * per_src >= ndm (every trial reads the one plane); stage 2 is data = stage
+ * 1's output, nsrc = its trials, per_src = the trials built from each,
+ * nchan = band (one band: out is [ndm][out_ld]).
+ * The table is arbitrary; because of the clamp no read leaves [0, n) of its
+ * row whatever it holds, and nothing is written outside the T samples of each
+ * output row.  pss_dedisperse's tile: a workgroup owns 2048 times of 8
+ * neighbouring trials of one source and one band -- the trials are cut into
+ * groups of 8 inside each source, so no workgroup reads two sources -- and a
+ * channel whose delays differ by at most 2044 samples among them is read once
+ * for all (staged in LDS), a wider one once per trial.  Every output is
+ * summed in increasing c by one thread, without atomics: the same input gives
+ * the same bits from run to run and whatever the alignment of data / ld /
+ * src_stride / out / out_ld; with nsrc = 1 and band >= nchan they are
+ * pss_dedisperse's bits.  No workspace.
+ * PSS_EINVAL (nothing launched) on a NULL pointer, nsrc < 1, nchan < 1,
+ * ndm < 1, per_src < 1, band < 1, ld < n, src_stride < nchan * ld,
+ * max_delay < 0, max_delay >= n or out_ld < T, and when ceil(T / 2048) * nb *
+ * (trial groups) exceeds 2^31 - 1 (the launch grid).
+ */
+int pss_dedisperse_banded(const float *data, int32_t nsrc, int64_t src_stride, int32_t nchan, int64_t n,
+                          int64_t ld, const int32_t *delays, int32_t ndm, int32_t per_src, int32_t max_delay,
+                          int32_t band, float *out, int64_t out_ld, void *stream);
+
+/*
  * RFI excision of a search-mode filterbank (extension, no reference
  * counterpart): data[nchan][ld] float32 (n samples per row), mask[nblk][nchan]
  * bytes (non-zero = flagged) over blocks of `block` samples, base[nchan] the

@@ -78,6 +78,8 @@ EXPORTS = {
     "pss_channelize": (ctypes.c_int, [c_vp, c_i32, c_i64, c_i64, c_vp, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp]),
     "pss_normal_add": (ctypes.c_int, [c_vp, c_i32, c_i64, c_i64, c_f32, c_u64, c_u32, c_vp]),
     "pss_dedisperse": (ctypes.c_int, [c_vp, c_i32, c_i64, c_i64, c_vp, c_i32, c_i32, c_vp, c_i64, c_vp]),
+    "pss_dedisperse_banded": (ctypes.c_int, [c_vp, c_i32, c_i64, c_i32, c_i64, c_i64, c_vp, c_i32, c_i32, c_i32, c_i32,
+                                             c_vp, c_i64, c_vp]),
     "pss_rfi_clean": (ctypes.c_int, [c_vp, c_i32, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp,
                                      c_vp]),
     "pss_boxcar_search": (ctypes.c_int, [c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_i64,

@@ -34,6 +34,22 @@
 //       Logical workgroup index = time tile * (trial groups) + trial group,
 //       dealt to the XCDs in contiguous runs: the groups of one time tile run
 //       together on one XCD and share its rows in that L2.
+//
+//   k_dedisperse_banded<VEC> : the same tile (dd_tile, shared) summed over one
+//       band of channels only, read from one of several source planes:
+//
+//         out[j * nb + s][t] = sum_{c in band s} src(j)[c][t + d(j, c)],
+//
+//       nb = ceil(nchan / band), src(j) = min(j / per_src, nsrc - 1).  Both
+//       stages of the sub-band dedispersion (telescope/subband.py) are calls of
+//       it.  The trials are cut into groups of 8 inside each source (per_src =
+//       5: groups of 5, 5, ..), so a workgroup reads one source.  Logical
+//       workgroup index = (time tile * nb + band) * (trial groups) + trial
+//       group, through the same run map: the bands and groups of one time tile
+//       run on one XCD.  With one source and one band it is k_dedisperse's
+//       sum, operation for operation.
+#include <algorithm>
+
 #include "pss_common.hpp"
 #include "pss_window.hpp"
 
@@ -79,30 +95,21 @@ __device__ __forceinline__ void dd_accum(float (*acc)[kDdS], const float *w, con
     __builtin_amdgcn_sched_barrier(0);
 }
 
-// (the pointers are separate __restrict__ parameters: the table is then known
-// not to alias `out`, and its wave-uniform loads become scalar loads)
+// One workgroup's tile: times t0 .. t0 + len (len <= kTB) of the nd <= kND trials
+// j0 .. (rows of `tab`, ntab entries each), summed over the channels
+// [c_lo, c_hi) of data[c][ld] in increasing c; trial j0 + j goes to o0 + j * orow.
 template <bool VEC>
-__global__ __launch_bounds__(kDdThreads) void k_dedisperse(const float *__restrict__ data,
-                                                           const int32_t *__restrict__ tab, float *__restrict__ out,
-                                                           DdArgs a) {
-    __shared__ __align__(16) float win[kCB][kWin];
-    const int tid = threadIdx.x;
-    // Workgroup id -> (time tile, trial group), groups fastest, through the XCD
-    // run map: the trial groups of one time tile then run on one XCD, side by
-    // side, and its L2 fetches each row once for all of them.
-    const uint2 id = xcd_run_pair((unsigned)a.ngroups);
-    const int g = (int)id.y;
-    const int64_t t0 = (int64_t)id.x * kTB;
-    const int j0 = g * kND;
-    const int nd = min(kND, a.ndm - j0);                       // trials of this group (>= 1)
-    const int len = (int)min((int64_t)kTB, a.T - t0);          // times of this tile (>= 1)
+__device__ __forceinline__ void dd_tile(float (*win)[kWin], const float *__restrict__ data,
+                                        const int32_t *__restrict__ tab, float *__restrict__ o0, int64_t orow,
+                                        int c_lo, int c_hi, int ntab, int j0, int nd, int64_t t0, int len, int64_t n,
+                                        int64_t ld, int max_delay, int tid) {
     float acc[kND][kDdS];
 #pragma unroll
     for (int j = 0; j < kND; ++j)
 #pragma unroll
         for (int k = 0; k < kDdS; ++k) acc[j][k] = 0.0f;
 
-    for (int c0 = 0; c0 < a.nchan; c0 += kCB) {
+    for (int c0 = c_lo; c0 < c_hi; c0 += kCB) {
         int d[kCB][kND];
         int64_t ws[kCB];
         bool staged[kCB];
@@ -111,13 +118,13 @@ __global__ __launch_bounds__(kDdThreads) void k_dedisperse(const float *__restri
             const int c = c0 + cb;
             staged[cb] = false;
             ws[cb] = 0;
-            if (c >= a.nchan) continue;
-            int dmin = a.max_delay, dmax = 0;
+            if (c >= c_hi) continue;
+            int dmin = max_delay, dmax = 0;
 #pragma unroll
             for (int j = 0; j < kND; ++j) {
                 // (a ragged group repeats its last trial: summed, never stored)
                 const int jj = j0 + min(j, nd - 1);
-                d[cb][j] = min(max(tab[(int64_t)jj * a.nchan + c], 0), a.max_delay);
+                d[cb][j] = min(max(tab[(int64_t)jj * ntab + c], 0), max_delay);
                 dmin = min(dmin, d[cb][j]);
                 dmax = max(dmax, d[cb][j]);
             }
@@ -127,16 +134,16 @@ __global__ __launch_bounds__(kDdThreads) void k_dedisperse(const float *__restri
             // the window's last needed sample is t0 + len - 1 + dmax <= n - 1
             const int need = (int)(t0 + dmax - ws[cb]) + len;  // <= 3 + kSpread + kTB < kWin
             // (samples at or past n, never needed, are zeros; ws >= 0: no HEAD)
-            stage_window<kDdThreads, kWin, VEC, false>(win[cb], data + (int64_t)c * a.ld, ws[cb], need, a.n, tid);
+            stage_window<kDdThreads, kWin, VEC, false>(win[cb], data + (int64_t)c * ld, ws[cb], need, n, tid);
         }
         __syncthreads();
 #pragma unroll
         for (int cb = 0; cb < kCB; ++cb) {
             const int c = c0 + cb;
-            if (c >= a.nchan) continue;
+            if (c >= c_hi) continue;
             // (one accumulate serves both paths: an if / else around two copies of
             // it joins the 64 accumulators in phis that cost 60 more registers)
-            const float *row = data + (int64_t)c * a.ld + t0;
+            const float *row = data + (int64_t)c * ld + t0;
 #pragma unroll
             for (int j = 0; j < kND; j += kNJ) {
                 int off[kNJ];
@@ -160,12 +167,66 @@ __global__ __launch_bounds__(kDdThreads) void k_dedisperse(const float *__restri
 #pragma unroll
     for (int j = 0; j < kND; ++j) {
         if (j < nd) {
-            float *o = out + (int64_t)(j0 + j) * a.out_ld + t0 + tid;
+            float *o = o0 + (int64_t)j * orow + t0 + tid;
 #pragma unroll
             for (int k = 0; k < kDdS; ++k)
                 if (tid + k * kDdThreads < len) o[k * kDdThreads] = acc[j][k];
         }
     }
+}
+
+// (the pointers are separate __restrict__ parameters: the table is then known
+// not to alias `out`, and its wave-uniform loads become scalar loads)
+template <bool VEC>
+__global__ __launch_bounds__(kDdThreads) void k_dedisperse(const float *__restrict__ data,
+                                                           const int32_t *__restrict__ tab, float *__restrict__ out,
+                                                           DdArgs a) {
+    __shared__ __align__(16) float win[kCB][kWin];
+    const int tid = threadIdx.x;
+    // Workgroup id -> (time tile, trial group), groups fastest, through the XCD
+    // run map: the trial groups of one time tile then run on one XCD, side by
+    // side, and its L2 fetches each row once for all of them.
+    const uint2 id = xcd_run_pair((unsigned)a.ngroups);
+    const int g = (int)id.y;
+    const int64_t t0 = (int64_t)id.x * kTB;
+    const int j0 = g * kND;
+    const int nd = min(kND, a.ndm - j0);                       // trials of this group (>= 1)
+    const int len = (int)min((int64_t)kTB, a.T - t0);          // times of this tile (>= 1)
+    dd_tile<VEC>(win, data, tab, out + (int64_t)j0 * a.out_ld, a.out_ld, 0, a.nchan, a.nchan, j0, nd, t0, len, a.n,
+                 a.ld, a.max_delay, tid);
+}
+
+// the banded sum's own arguments, beside DdArgs (whose ngroups counts the trial
+// groups of all sources): nsrc sources are in use, each but the last owns
+// per_src trials = gps groups, the last one the rest
+struct DdBandArgs {
+    int64_t src_stride;
+    int32_t band, nbands, per_src, nsrc, gps;
+};
+
+template <bool VEC>
+__global__ __launch_bounds__(kDdThreads) void k_dedisperse_banded(const float *__restrict__ data,
+                                                                  const int32_t *__restrict__ tab,
+                                                                  float *__restrict__ out, DdArgs a, DdBandArgs b) {
+    __shared__ __align__(16) float win[kCB][kWin];
+    const int tid = threadIdx.x;
+    // Workgroup id -> (time tile, band, trial group), groups fastest: the bands
+    // and groups of one time tile run on one XCD and share its rows in that L2
+    const uint2 id = xcd_run_pair((unsigned)a.ngroups);
+    const int g = (int)id.y;
+    const int s = (int)(id.x % (unsigned)b.nbands);
+    const int64_t t0 = (int64_t)(id.x / (unsigned)b.nbands) * kTB;
+    // the group's source, and its trials inside it: a group ends with its source
+    const int q = min(g / b.gps, b.nsrc - 1);
+    const int j0 = q * b.per_src + (g - q * b.gps) * kND;
+    const int jend = q == b.nsrc - 1 ? a.ndm : (q + 1) * b.per_src;
+    const int nd = min(kND, jend - j0);                        // (>= 1)
+    const int len = (int)min((int64_t)kTB, a.T - t0);
+    const int c_lo = s * b.band;
+    const int c_hi = c_lo + min(b.band, a.nchan - c_lo);
+    PSS_DASSERT(q >= 0 && j0 >= 0 && nd >= 1 && j0 + nd <= a.ndm && len >= 1 && c_lo < c_hi && c_hi <= a.nchan);
+    dd_tile<VEC>(win, data + (int64_t)q * b.src_stride, tab, out + ((int64_t)j0 * b.nbands + s) * a.out_ld,
+                 (int64_t)b.nbands * a.out_ld, c_lo, c_hi, a.nchan, j0, nd, t0, len, a.n, a.ld, a.max_delay, tid);
 }
 
 extern "C" {
@@ -195,6 +256,54 @@ int pss_dedisperse(const float *data, int32_t nchan, int64_t n, int64_t ld, cons
         k_dedisperse<true><<<grid, dim3(kDdThreads), 0, (hipStream_t)stream>>>(data, delays, out, a);
     else
         k_dedisperse<false><<<grid, dim3(kDdThreads), 0, (hipStream_t)stream>>>(data, delays, out, a);
+    LAUNCHCHK();
+    return PSS_OK;
+}
+
+int pss_dedisperse_banded(const float *data, int32_t nsrc, int64_t src_stride, int32_t nchan, int64_t n, int64_t ld,
+                          const int32_t *delays, int32_t ndm, int32_t per_src, int32_t max_delay, int32_t band,
+                          float *out, int64_t out_ld, void *stream) {
+    if (!data) return fail(PSS_EINVAL, "dedisperse_banded: data is NULL");
+    if (!delays) return fail(PSS_EINVAL, "dedisperse_banded: delays is NULL");
+    if (!out) return fail(PSS_EINVAL, "dedisperse_banded: out is NULL");
+    if (nsrc < 1) return fail(PSS_EINVAL, "dedisperse_banded: nsrc %d < 1", nsrc);
+    if (nchan < 1) return fail(PSS_EINVAL, "dedisperse_banded: nchan %d < 1", nchan);
+    if (ndm < 1) return fail(PSS_EINVAL, "dedisperse_banded: ndm %d < 1", ndm);
+    if (per_src < 1) return fail(PSS_EINVAL, "dedisperse_banded: per_src %d < 1", per_src);
+    if (band < 1) return fail(PSS_EINVAL, "dedisperse_banded: band %d < 1", band);
+    if (ld < n) return fail(PSS_EINVAL, "dedisperse_banded: ld %lld < n %lld", (long long)ld, (long long)n);
+    if ((__int128)src_stride < (__int128)nchan * ld)
+        return fail(PSS_EINVAL, "dedisperse_banded: src_stride %lld < nchan %d x ld %lld", (long long)src_stride, nchan,
+                    (long long)ld);
+    if (max_delay < 0) return fail(PSS_EINVAL, "dedisperse_banded: max_delay %d < 0", max_delay);
+    if (max_delay >= n)
+        return fail(PSS_EINVAL, "dedisperse_banded: max_delay %d >= n %lld", max_delay, (long long)n);
+    const int64_t T = n - max_delay;
+    if (out_ld < T) return fail(PSS_EINVAL, "dedisperse_banded: out_ld %lld < %lld output samples", (long long)out_ld,
+                                (long long)T);
+    // the sources in use; all but the last own per_src trials = gps groups
+    const int64_t nsu = std::min<int64_t>(nsrc, ((int64_t)ndm + per_src - 1) / per_src);
+    const int64_t last = ndm - (nsu - 1) * per_src;
+    const int64_t gps = nsu > 1 ? ((int64_t)per_src + kND - 1) / kND : (last + kND - 1) / kND;
+    const int64_t ngroups = (nsu - 1) * gps + (last + kND - 1) / kND;        // <= ndm
+    const int64_t nbands = ((int64_t)nchan + band - 1) / band;
+    const int64_t ntiles = (T + kTB - 1) / kTB;
+    if (ntiles > (int64_t)0x7fffffff / nbands)
+        return fail(PSS_EINVAL, "dedisperse_banded: %lld time tiles x %lld bands exceed 2^31 - 1 workgroups",
+                    (long long)ntiles, (long long)nbands);
+    const dim3 grid = grid_1d("dedisperse_banded", ntiles * nbands, "time tiles x bands", ngroups, "trial groups");
+    if (!grid.x) return PSS_EINVAL;
+    DdArgs a;
+    a.n = n; a.ld = ld; a.nchan = nchan; a.ndm = ndm; a.max_delay = max_delay;
+    a.ngroups = (int32_t)ngroups; a.out_ld = out_ld; a.T = T;
+    DdBandArgs b;
+    b.src_stride = src_stride; b.band = band; b.nbands = (int32_t)nbands; b.per_src = per_src;
+    b.nsrc = (int32_t)nsu; b.gps = (int32_t)gps;
+    // 16-B loads of the staged windows need every source's rows on the 16-B grid.  Same bits.
+    if (on_grid16(data, ld) && (nsu == 1 || src_stride % 4 == 0))
+        k_dedisperse_banded<true><<<grid, dim3(kDdThreads), 0, (hipStream_t)stream>>>(data, delays, out, a, b);
+    else
+        k_dedisperse_banded<false><<<grid, dim3(kDdThreads), 0, (hipStream_t)stream>>>(data, delays, out, a, b);
     LAUNCHCHK();
     return PSS_OK;
 }

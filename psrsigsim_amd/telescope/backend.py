@@ -7,6 +7,7 @@ from .. import _engine, _lib
 from .plane import DedispersedPlane, cluster_cells  # noqa: F401
 from .channelize import ChannelizeStage
 from .dedisperse import DedisperseStage
+from .subband import SubbandStage, SubbandPlan  # noqa: F401
 from .pulse_search import PulseSearchStage, BoxcarPlane, PulseCandidates, CANDIDATE_DTYPE  # noqa: F401
 from .pulse_search import candidates_from_cells  # noqa: F401
 from .periodicity import PeriodicityStage, HarmonicPlane, PeriodCandidates, PERIOD_DTYPE  # noqa: F401
@@ -17,11 +18,12 @@ from .rfi import RfiStage, RfiMask, inject_rfi  # noqa: F401
 from .ffa import FFAStage, FFAPlane, FFACandidates, FFA_DTYPE, ffa_candidates_from_cells  # noqa: F401
 
 __all__ = ['Backend', 'DedispersedPlane', 'BoxcarPlane', 'PulseCandidates', 'HarmonicPlane', 'PeriodCandidates',
-           'FoldedCandidates', 'AccelPlane', 'AccelCandidates', 'RfiMask', 'inject_rfi', 'FFAPlane', 'FFACandidates']
+           'FoldedCandidates', 'AccelPlane', 'AccelCandidates', 'RfiMask', 'inject_rfi', 'FFAPlane', 'FFACandidates',
+           'SubbandPlan']
 
 
-class Backend(ChannelizeStage, RfiStage, DedisperseStage, PulseSearchStage, PeriodicityStage, AccelStage, FoldStage,
-              FFAStage):
+class Backend(ChannelizeStage, RfiStage, DedisperseStage, SubbandStage, PulseSearchStage, PeriodicityStage, AccelStage,
+              FoldStage, FFAStage):
     def __init__(self, samprate=None, name=None):
         self._name = name
         self._samprate = make_quant(samprate, "MHz")

@@ -15,7 +15,10 @@ class DedispersedPlane(object):
     ``delays``    the host table, int32 [nDM][C_local] samples
     ``samprate``  sample rate of the series, MHz
     ``ref_freq``  the frequency the delays refer to, MHz
-    ``max_delay`` the table's maximum, samples"""
+    ``max_delay`` the table's maximum, samples
+    ``subband``   None, or the :class:`SubbandPlan` of a plane that :meth:`Backend.subband_dedisperse` made
+                  (``delays`` is then its effective table)"""
+    subband = None
 
     def __init__(self, data, dms, delays, samprate, ref_freq, max_delay):
         self.data = data
