@@ -381,6 +381,35 @@ int pss_quantize_tmajor(const float *data, int32_t nchan, int64_t ld, int64_t ns
                         const float *scl, const float *offs, int32_t nbits, void *out, void *stream);
 
 /*
+ * Search-mode input (extension, no reference counterpart): the inverse of
+ * pss_quantize_tmajor.  in[r][t][p][c] holds nbits-bit codes, nbits in
+ * {8, 4, 2}, channel fastest as a SUBINT row's DATA column: every time sample
+ * is npol runs of nchan*nbits/8 bytes, the lower-numbered channel in the more
+ * significant bits of its byte; nchan*nbits must fill whole bytes.  scl / offs
+ * are float32 [nrows][npol][nchan] device arrays (DAT_SCL / DAT_OFFS as
+ * stored: a 0 scale is a 0 scale), wts float32 [nrows][nchan] or NULL (all
+ * ones).  out is [nchan][ld] float32; row r fills the columns [r*nsblk,
+ * (r+1)*nsblk) counted from the `out` pointer (offset out by whole rows of
+ * nsblk samples and in / scl / offs / wts by whole rows to work in chunks):
+ *   v_p = fmaf((float)code - zero_off, scl[r][p][c], offs[r][p][c])    p < nsum
+ *   x   = (nsum == 2 ? v_0 + v_1 : v_0) * w[r][c]
+ *   out[flip ? nchan-1-c : c][r*nsblk + t] = x
+ * in float32, one rounding per operation on every path.  npol is 1, 2 or 4,
+ * nsum 1 or 2 and <= npol; polarisations at or beyond nsum are never read.
+ * Whole-dword loads and 16-B stores when the byte runs are a multiple of 4,
+ * `in` is 4-B aligned, out and ld are on the 16-B grid and nsblk % 4 == 0;
+ * element by element otherwise, the same bits.  No atomics: the same input
+ * gives the same bits from run to run.
+ * PSS_EINVAL (nothing launched) on NULL in / scl / offs / out, nbits, npol or
+ * nsum out of range, channel bits that do not fill whole bytes, nsblk < 1,
+ * ld < nrows*nsblk or nchan > 65535; PSS_OK with nothing launched when
+ * nchan <= 0 or nrows <= 0.
+ */
+int pss_unpack_tmajor(const void *in, int32_t nchan, int32_t npol, int32_t nsum, int64_t nsblk, int64_t nrows,
+                      const float *scl, const float *offs, const float *wts, float zero_off, int32_t nbits,
+                      int32_t flip, float *out, int64_t ld, void *stream);
+
+/*
  * Baseband channeliser and detector (extension, no reference counterpart).
  * x[npol][ld] float32 voltages (npol = 1 or 2, n samples per row), C = nchan a
  * power of two in [16, 4096], L = 2 C, T = ntap in [1, 8], h[T L] the

@@ -75,6 +75,8 @@ EXPORTS = {
     "pss_chi2_fill": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i64, c_f32, c_u64, c_u32, c_u32, c_vp]),
     "pss_chan_stats": (ctypes.c_int, [c_vp, c_i32, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "pss_quantize_tmajor": (ctypes.c_int, [c_vp, c_i32, c_i64, c_i64, c_i64, c_vp, c_vp, c_i32, c_vp, c_vp]),
+    "pss_unpack_tmajor": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_f32, c_i32, c_i32,
+                                         c_vp, c_i64, c_vp]),
     "pss_channelize": (ctypes.c_int, [c_vp, c_i32, c_i64, c_i64, c_vp, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp]),
     "pss_normal_add": (ctypes.c_int, [c_vp, c_i32, c_i64, c_i64, c_f32, c_u64, c_u32, c_vp]),
     "pss_dedisperse": (ctypes.c_int, [c_vp, c_i32, c_i64, c_i64, c_vp, c_i32, c_i32, c_vp, c_i64, c_vp]),

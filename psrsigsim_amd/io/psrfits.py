@@ -36,7 +36,9 @@ Search mode (``PSRFITS(path, obs_mode="SEARCH")``, no template; an extension:
 the reference leaves it a TODO): the float32 [nchan][nsamp] product is
 quantised to 8 / 4 / 2 bits and transposed to the file's time-major order on
 the device, in chunks of rows (``PSRFITS._save_search``); ``read_search_data``
-unpacks such a file on the host.
+unpacks such a file on the host, and ``load_search_signal``
+(``PSRFITS(path).load_search()``) on the device, into a FilterBankSignal the
+search stages take.
 """
 import logging
 import math
@@ -45,7 +47,8 @@ import numpy as np
 
 from .._units import Quantity
 
-__all__ = ["PSRFITS", "read_psrfits", "read_fits", "read_search_data", "template_profile"]
+__all__ = ["PSRFITS", "read_psrfits", "read_fits", "read_search_data", "load_search_signal",
+           "template_profile"]
 
 log = logging.getLogger("psrsigsim_amd")
 
@@ -130,6 +133,20 @@ def _set_cards(cards, values):
     return out
 
 
+def _hdu_size(hdr, index):
+    """(name, unpadded data bytes) of the HDU with the header ``hdr``, the
+    ``index``-th of its file."""
+    if "SIMPLE" in hdr:
+        size = 0
+        if int(hdr.get("NAXIS", 0)) > 0:
+            size = abs(int(hdr["BITPIX"])) // 8
+            for a in range(1, int(hdr["NAXIS"]) + 1):
+                size *= int(hdr["NAXIS%d" % a])
+        return "PRIMARY", size
+    name = str(hdr.get("EXTNAME", "HDU%d" % index)).strip()
+    return name, int(hdr["NAXIS1"]) * int(hdr["NAXIS2"]) + int(hdr.get("PCOUNT", 0))
+
+
 def _raw_hdus(path):
     """[{name, cards (80-char images, END excluded), hdr (parsed), data
     (bytes, unpadded)}] of a FITS file, in file order."""
@@ -146,15 +163,7 @@ def _raw_hdus(path):
             if c[:8].rstrip() == "END":
                 break
             cards.append(c)
-        if "SIMPLE" in hdr:
-            name, size = "PRIMARY", 0
-            if int(hdr.get("NAXIS", 0)) > 0:
-                size = abs(int(hdr["BITPIX"])) // 8
-                for a in range(1, int(hdr["NAXIS"]) + 1):
-                    size *= int(hdr["NAXIS%d" % a])
-        else:
-            name = str(hdr.get("EXTNAME", "HDU%d" % len(out))).strip()
-            size = int(hdr["NAXIS1"]) * int(hdr["NAXIS2"]) + int(hdr.get("PCOUNT", 0))
+        name, size = _hdu_size(hdr, len(out))
         out.append({"name": name, "cards": cards, "hdr": hdr, "data": buf[end:end + size]})
         pos = end + -(-size // _BLOCK) * _BLOCK
     return out
@@ -623,6 +632,211 @@ class PSRFITS(object):
             f.write(b"\0" * ((-nrows * (head.itemsize + rowbytes)) % _BLOCK))
         self.nchan, self.nrows, self.nsblk, self.tbin, self.npol = nchan, nrows, nsblk, tbin, 1
 
+    # -- load ---------------------------------------------------------------
+    def load_search(self, rows=None, apply_weights=True, period=None, max_stage_bytes=256 << 20):
+        """The search-mode file at ``path`` as a device FilterBankSignal
+        (:func:`load_search_signal`)."""
+        if self.path is None:
+            raise ValueError("no input path")
+        return load_search_signal(self.path, rows=rows, apply_weights=apply_weights, period=period,
+                                  max_stage_bytes=max_stage_bytes)
+
+
+# pinned / staging buffer pairs of load_search_signal (tools/search_in_bench.py
+# times one pair against two)
+_LOAD_BUFFERS = 2
+
+
+def _find_subint(path):
+    """(primary header, SUBINT header, byte offset of the SUBINT table) of a
+    FITS file, through a memory map: only the header blocks are read."""
+    import mmap
+    with open(path, "rb") as f:
+        mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
+    try:
+        prim, pos = None, 0
+        while pos < len(mm):
+            hdr, pos = _parse_header(mm, pos)
+            if "SIMPLE" in hdr:
+                prim = hdr
+            elif str(hdr.get("EXTNAME", "")).strip() == "SUBINT" and hdr.get("XTENSION") == "BINTABLE":
+                if prim is None:
+                    raise ValueError("%s: a SUBINT table without a primary header" % path)
+                return prim, hdr, pos
+            pos += -(-_hdu_size(hdr, 0)[1] // _BLOCK) * _BLOCK
+    finally:
+        mm.close()
+    raise ValueError("%s holds no SUBINT table" % path)
+
+
+def _search_layout(path, rows):
+    """Everything :func:`load_search_signal` decides on the host, before any
+    device use: the file's geometry, the selected rows, the polarisations to
+    sum, the band's direction, and the SUBINT table as a memory map."""
+    prim, sub, pos = _find_subint(path)
+    nbits, signint, nbin = int(sub.get("NBITS", 0)), int(sub.get("SIGNINT", 0) or 0), int(sub.get("NBIN", 1) or 1)
+    npol, pol_type = int(sub.get("NPOL", 1)), str(sub.get("POL_TYPE", "")).strip()
+    if nbits not in (8, 4, 2):
+        raise NotImplementedError("search-mode samples of NBITS = %d (8, 4 and 2 are read)" % nbits)
+    if signint == 1:
+        raise NotImplementedError("signed samples (SIGNINT = 1)")
+    if nbin != 1:
+        raise NotImplementedError("NBIN = %d: not a search-mode table (NBIN = 1)" % nbin)
+    if npol == 1:
+        nsum = 1
+    elif npol == 2 or (npol == 4 and pol_type.startswith("AABB")):
+        nsum = 2                                               # AA + BB
+    elif npol == 4 and pol_type == "IQUV":
+        nsum = 1                                               # I
+    else:
+        raise NotImplementedError("NPOL = %d with POL_TYPE %r (total intensity comes from NPOL 1, NPOL 2, "
+                                  "AABB.. or IQUV)" % (npol, pol_type))
+    nchan, nsblk, nrows = int(sub["NCHAN"]), int(sub["NSBLK"]), int(sub["NAXIS2"])
+    if nchan < 1 or nsblk < 1 or (nchan * nbits) % 8:
+        raise ValueError("%s: NCHAN %d, NSBLK %d at %d bits" % (path, nchan, nsblk, nbits))
+    tbin = float(sub["TBIN"])
+    if not tbin > 0.0:
+        raise ValueError("%s: TBIN %r" % (path, tbin))
+    r0, r1 = (0, nrows) if rows is None else (int(rows[0]), int(rows[1]))
+    if not (0 <= r0 < r1 <= nrows):
+        raise ValueError("rows %r outside the %d rows of %s" % (rows, nrows, path))
+    # the DATA column as plain bytes, whatever its TDIM says
+    names = [str(sub["TTYPE%d" % i]).strip() for i in range(1, int(sub["TFIELDS"]) + 1)]
+    missing = [c for c in ("DAT_FREQ", "DAT_WTS", "DAT_OFFS", "DAT_SCL", "DATA") if c not in names]
+    if missing:
+        raise ValueError("%s: the SUBINT table lacks %s" % (path, ", ".join(missing)))
+    flat = dict(sub)
+    flat.pop("TDIM%d" % (names.index("DATA") + 1), None)
+    dt = _table_dtype(flat)
+    databytes = nsblk * npol * nchan * nbits // 8
+    sizes = {"DATA": databytes, "DAT_FREQ": 8 * nchan, "DAT_WTS": 4 * nchan, "DAT_OFFS": 4 * npol * nchan,
+             "DAT_SCL": 4 * npol * nchan}
+    for name, want in sizes.items():
+        if dt.fields[name][0].itemsize != want:
+            raise ValueError("%s: column %s holds %d bytes a row, %d channels x %d polarisations x %d samples of %d "
+                             "bits need %d" % (path, name, dt.fields[name][0].itemsize, nchan, npol, nsblk, nbits, want))
+    rec = np.memmap(path, dtype=dt, mode="r", offset=pos, shape=(nrows,))
+    freq = np.asarray(rec["DAT_FREQ"], dtype=np.float64).reshape(nrows, nchan)
+    if (freq != freq[0]).any():
+        raise ValueError("%s: DAT_FREQ differs between rows" % path)
+    step = np.diff(freq[0])
+    if not ((step > 0).all() or (step < 0).all()):
+        raise ValueError("%s: DAT_FREQ is not monotonic" % path)
+    if "OBSFREQ" not in prim or "OBSBW" not in prim:
+        raise ValueError("%s: no OBSFREQ / OBSBW" % path)
+    return dict(prim=prim, sub=sub, rec=rec, pos=pos, data_off=dt.fields["DATA"][1], databytes=databytes,
+                nbits=nbits, npol=npol, nsum=nsum, pol_type=pol_type, nchan=nchan, nsblk=nsblk, nrows=nrows,
+                tbin=tbin, r0=r0, r1=r1, freq=freq[0], flip=bool(nchan > 1 and step[0] < 0),
+                zero_off=float(sub.get("ZERO_OFF", 0.0) or 0.0))
+
+
+def load_search_signal(path, rows=None, apply_weights=True, period=None, max_stage_bytes=256 << 20):
+    """A search-mode PSRFITS file as a search-mode FilterBankSignal on the
+    device (extension): the inverse of :meth:`PSRFITS.save` in search mode, and
+    a reader of foreign files of the same kind -- 8-, 4- or 2-bit unsigned
+    samples, NPOL 1, NPOL 2 or ``AABB..`` (the first two polarisations are
+    summed) or ``IQUV`` (the first is taken).  ``NotImplementedError`` names
+    anything else (other NBITS, SIGNINT = 1, NBIN != 1, another POL_TYPE).
+
+    The headers and the small SUBINT columns are read on the host through a
+    memory map of the table.  The DATA column of the rows ``rows=(r0, r1)``
+    (default: all) goes to the device in chunks of at most ``max_stage_bytes``
+    packed bytes -- file to a pinned buffer, pinned buffer to a staging
+    buffer, ``pss_unpack_tmajor`` from there into the final [nchan][nsamp]
+    float32 tensor (row stride on the 16-B grid) -- with two buffer pairs, so
+    that the host reads chunk k + 1 from the file while the device copies and
+    unpacks chunk k; the only host waits are for a pinned buffer's previous
+    copy.  Neither the DATA column nor a float copy of it is ever held whole
+    on the host.  Every sample is
+
+        (sum_p ((code - ZERO_OFF) * DAT_SCL[p] + DAT_OFFS[p])) * DAT_WTS
+
+    in float32 (``apply_weights=False``: no weights).
+
+    ``dat_freq`` is row 0's DAT_FREQ as the file gives it (this package's
+    files hold channel lower edges there, foreign files centres; the search
+    stages use ``dat_freq`` either way); a descending band is flipped, so that
+    ``dat_freq`` ascends.  ``ValueError`` for a DAT_FREQ that is not monotonic
+    or differs between rows, and for ``rows`` outside the file.  ``fcent`` and
+    ``bw`` are OBSFREQ and |OBSBW|, ``samprate`` 1e-6 / TBIN MHz, ``dm`` the
+    DM card (None when absent or 0).  The signal is one subint spanning
+    ``tobs`` unless ``period`` (s) is given: then ``sublen = period`` and
+    ``nsub = round(tobs / period)``, as ``make_pulses`` leaves a search-mode
+    signal.  ``signal.psrfits`` records nbits, nsblk, nrows, npol, pol_type,
+    zero_off, nsuboffs, flipped, weights (row 0's DAT_WTS in output channel
+    order) and the two header dicts."""
+    lay = _search_layout(path, rows)
+    nchan, npol, nsblk, nbits = lay["nchan"], lay["npol"], lay["nsblk"], lay["nbits"]
+    r0, r1, rec, databytes, flip = lay["r0"], lay["r1"], lay["rec"], lay["databytes"], lay["flip"]
+    n = r1 - r0
+    f32 = lambda col, width: np.ascontiguousarray(np.asarray(rec[col][r0:r1], dtype=np.float32).reshape(n, width))
+    scl, offs = f32("DAT_SCL", npol * nchan), f32("DAT_OFFS", npol * nchan)
+
+    import torch
+    from .. import _engine, _lib
+    from ..signal import FilterBankSignal
+    from .._units import make_quant
+    lib = _lib.lib()
+    dev = _engine.device()
+    d_scl, d_offs = _engine.to_dev(scl), _engine.to_dev(offs)
+    d_wts = _engine.to_dev(f32("DAT_WTS", nchan)) if apply_weights else None
+    nsamp = n * nsblk
+    ld = (nsamp + 3) // 4 * 4                                  # rows on the 16-B grid, as channelize
+    out = torch.empty((nchan, ld), dtype=torch.float32, device=dev)[:, :nsamp]
+    chunk = int(max(1, min(n, int(max_stage_bytes) // databytes)))
+    nbuf = min(_LOAD_BUFFERS, -(-n // chunk))
+    host = [torch.empty(chunk * databytes, dtype=torch.uint8).pin_memory() for _ in range(nbuf)]
+    stage = [torch.empty(chunk * databytes, dtype=torch.uint8, device=dev) for _ in range(nbuf)]
+    copied = [None] * nbuf
+    raw = np.memmap(path, dtype=np.uint8, mode="r", offset=lay["pos"], shape=(lay["nrows"], rec.dtype.itemsize))
+    raw = raw[:, lay["data_off"]:lay["data_off"] + databytes]
+    for k, a in enumerate(range(r0, r1, chunk)):
+        b, m = k % nbuf, min(chunk, r1 - a)
+        if copied[b] is not None:
+            copied[b].synchronize()                            # the copy that last read this pinned buffer
+        host[b].numpy()[:m * databytes].reshape(m, databytes)[...] = raw[a:a + m]
+        stage[b][:m * databytes].copy_(host[b][:m * databytes], non_blocking=True)
+        copied[b] = torch.cuda.Event()
+        copied[b].record()
+        rc = lib.pss_unpack_tmajor(stage[b].data_ptr(), nchan, npol, lay["nsum"], nsblk, m,
+                                   d_scl.data_ptr() + 4 * (a - r0) * npol * nchan,
+                                   d_offs.data_ptr() + 4 * (a - r0) * npol * nchan,
+                                   d_wts.data_ptr() + 4 * (a - r0) * nchan if d_wts is not None else None,
+                                   lay["zero_off"], nbits, 1 if flip else 0, out.data_ptr() + 4 * (a - r0) * nsblk, ld,
+                                   _engine.stream_ptr())
+        _lib.check(rc, "unpack_tmajor")
+
+    prim, sub, tbin = lay["prim"], lay["sub"], lay["tbin"]
+    sig = FilterBankSignal(float(prim["OBSFREQ"]), abs(float(prim["OBSBW"])), Nsubband=nchan, fold=False,
+                           dtype=np.float32)
+    sig._samprate = make_quant(1e-6 / tbin, 'MHz')             # (set here: the constructor warns below Nyquist)
+    order = slice(None, None, -1) if flip else slice(None)
+    sig._dat_freq = Quantity(lay["freq"][order].copy(), 'MHz')
+    sig._buf = out
+    sig._ncols = nsamp
+    sig._nsamp = nsamp
+    sig._pending = None
+    tobs = nsamp * tbin
+    sig._tobs = make_quant(tobs, 's')
+    if period:
+        sig._sublen = make_quant(float(period), 's')
+        sig._nsub = int(np.round(tobs / float(period)))
+    else:
+        sig._sublen = sig._tobs
+        sig._nsub = 1
+    sig._set_draw_norm(df=1)
+    sig._Smax = None
+    dm = sub.get("DM")
+    sig._dm = make_quant(float(dm), 'pc/cm^3') if dm else None
+    sig._delay = None
+    sig._null_error = None
+    sig._null_checks = []
+    wts0 = np.asarray(rec["DAT_WTS"][0], dtype=np.float32).reshape(nchan)
+    sig.psrfits = dict(nbits=nbits, nsblk=nsblk, nrows=n, npol=npol, pol_type=lay["pol_type"],
+                       zero_off=lay["zero_off"], nsuboffs=int(sub.get("NSUBOFFS", 0) or 0), flipped=flip,
+                       weights=wts0[order].copy(), primary=prim, subint=sub)
+    return sig
+
 
 def read_search_data(path):
     """A search-mode file of :meth:`PSRFITS.save` on the host: ``(codes,
@@ -725,16 +939,10 @@ def read_fits(path):
     pos = 0
     while pos < len(buf):
         hdr, pos = _parse_header(buf, pos)
+        name, size = _hdu_size(hdr, len(out))
         if "SIMPLE" in hdr:
-            name, size = "PRIMARY", 0
-            if int(hdr.get("NAXIS", 0)) > 0:
-                size = abs(int(hdr["BITPIX"])) // 8
-                for a in range(1, int(hdr["NAXIS"]) + 1):
-                    size *= int(hdr["NAXIS%d" % a])
             out[name] = (hdr, None)
         else:
-            name = str(hdr.get("EXTNAME", "HDU%d" % len(out))).strip()
-            size = int(hdr["NAXIS1"]) * int(hdr["NAXIS2"]) + int(hdr.get("PCOUNT", 0))
             rec = None
             if hdr.get("XTENSION") == "BINTABLE":
                 try:
