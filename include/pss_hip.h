@@ -709,6 +709,79 @@ int pss_accel_resample(const float *x, int32_t nser, int64_t T, int64_t ld, cons
                        int64_t out_ld, void *stream);
 
 /*
+ * Whitening of a spectrum before pss_harmonic_search (extension, no reference
+ * counterpart), two entry points: the lower median of the power over ragged
+ * blocks of bins -- the noise spectrum -- and the division of every bin by the
+ * median interpolated between block centres, with known interference lines
+ * replaced by a neutral value.  spec[ndm][ld] is a complex spectrum
+ * (interleaved float32 re / im, ld in complex elements, nbin usable bins per
+ * row, as in pss_harmonic_search).  edges[nblk + 1] is a device table of
+ * int64, strictly increasing, 0 <= edges[0], edges[nblk] == nbin, every width
+ * edges[b + 1] - edges[b] in [1, 256]: block b holds the bins edges[b] ..
+ * edges[b + 1] - 1.  The entry points take the device pointer alone and no
+ * host copy: the caller validates the table (Backend.whiten_plan builds it on
+ * the host).  With a table that breaks these rules the results are not
+ * defined, but memory is safe: a block is taken as [e, e + w), e =
+ * min(max(edges[b], 0), nbin), w = min(max(edges[b + 1], e), e + 256, nbin) -
+ * e, so that no read leaves a row whatever the table holds (w = 0 gives a NaN
+ * median), and the whitening reads spec and zap by the bin's own index only.
+ * All arithmetic is IEEE float32, every line one rounded operation, no fused
+ * multiply-add; division and square root are correctly rounded.
+ *
+ * pss_spectrum_medians:
+ *   P[k]      = (re_k * re_k) + (im_k * im_k)                     k < nbin
+ *   key(P)    = 0xFFFFFFFF if P is a NaN, else the bits of P (P >= +0: the
+ *               bits order as the values do)
+ *   med[j * med_ld + b] = the power whose key stands at sorted index (w - 1) / 2
+ *               of the w keys of block b of trial j (the lower median); a NaN
+ *               key gives the canonical NaN 0x7FC00000
+ * A selection is exact, so the bits depend on neither the algorithm, the tile,
+ * the alignment of spec / ld / med_ld nor the run.  Bins below edges[0] enter
+ * no block.  Nothing is written outside med[j * med_ld + 0 .. nblk).  A wave
+ * owns a block and selects by radix on the 32 key bits (ballots and population
+ * counts); a workgroup owns 32 consecutive blocks of one trial.
+ *
+ * pss_spectrum_whiten, with d_b = edges[b] + edges[b + 1] - 1 (twice the centre
+ * of block b, an integer) and m = med + j * med_ld:
+ *   norm(k) = m[0]                 if 2 k < d_0 or nblk == 1
+ *           = m[nblk - 1]          if 2 k >= d_{nblk-1}
+ *           = otherwise, with d_b <= 2 k < d_{b+1}:
+ *               f    = float(2 k - d_b) / float(d_{b+1} - d_b)   (both conversions exact)
+ *               diff = m[b + 1] - m[b]
+ *               t    = diff * f
+ *               norm = m[b] + t
+ *   q       = LN2 / norm                       LN2 = 0x3F317218
+ *   s       = sqrt(q) if 0 < norm < inf, else 0   (a NaN norm: 0)
+ *   out[j * out_ld + k] = (re_k * s, im_k * s)                    k < nbin
+ * with two rules that take precedence, in this order: a bin k < edges[0] is
+ * written as (0, 0); a bin with zap != NULL and zap[k] != 0 is written as
+ * (1, 0).  zap is NULL or one uint8[nbin] device table shared by all trials.
+ * The median of an exp(1) power of mean mu is mu ln 2: the whitened spectrum of
+ * noise has unit mean power and pss_harmonic_search takes it with scale = 1; a
+ * zapped bin has exactly the mean power, adds 0 to H - h and can neither make
+ * nor spoil a candidate.  out may be spec itself with out_ld == ld (in place)
+ * or must not overlap it at all; the bits are the same either way, and depend
+ * on neither the tile, the alignment of spec / ld / out / out_ld nor the run.
+ * (In place is why there are two entry points: a bin's norm takes the medians
+ * of both neighbouring blocks, which a fused kernel would read while another
+ * workgroup rewrites them.)  The columns [nbin, out_ld) of a row, the Nyquist
+ * bin among them, are never written, and nothing else outside out[j * out_ld +
+ * 0 .. nbin).  A workgroup owns 1024 bins of one trial and stages the centres
+ * and medians that bracket them in LDS.  No atomics, no workspace beyond med.
+ *
+ * PSS_EINVAL (nothing launched) on a NULL pointer other than zap, ndm < 1,
+ * nbin < 1, nblk < 1, nblk > nbin, ld < nbin, med_ld < nblk, for the whitening
+ * out_ld < nbin and an out that overlaps spec without being spec with out_ld
+ * == ld, and when ceil(nblk / 32) * ndm (medians) or ceil(nbin / 1024) * ndm
+ * (whitening) exceeds 2^31 - 1 (the launch grid).
+ */
+int pss_spectrum_medians(const float *spec, int32_t ndm, int64_t nbin, int64_t ld, const int64_t *edges,
+                         int32_t nblk, float *med, int64_t med_ld, void *stream);
+int pss_spectrum_whiten(const float *spec, int32_t ndm, int64_t nbin, int64_t ld, const int64_t *edges,
+                        int32_t nblk, const float *med, int64_t med_ld, const uint8_t *zap, float *out,
+                        int64_t out_ld, void *stream);
+
+/*
  * Fast folding search of a DM-time plane (extension, no reference
  * counterpart), three entry points: the time scrunch, the folding transform
  * and the search of its profiles.  Common to all three: all arithmetic on data

@@ -92,6 +92,9 @@ EXPORTS = {
                                        c_vp, c_vp]),
     "pss_accel_resample": (ctypes.c_int, [c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_i32, c_i64, c_vp, c_i64,
                                           c_vp]),
+    "pss_spectrum_medians": (ctypes.c_int, [c_vp, c_i32, c_i64, c_i64, c_vp, c_i32, c_vp, c_i64, c_vp]),
+    "pss_spectrum_whiten": (ctypes.c_int, [c_vp, c_i32, c_i64, c_i64, c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_i64,
+                                           c_vp]),
     "pss_ffa_scrunch": (ctypes.c_int, [c_vp, c_i32, c_i64, c_i64, c_vp, c_i32, c_vp, c_i64, c_vp]),
     "pss_ffa_transform": (ctypes.c_int, [c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "pss_ffa_profile_search": (ctypes.c_int, [c_vp, c_i32, c_i64, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp,

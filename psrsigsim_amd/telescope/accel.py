@@ -22,6 +22,7 @@ class AccelPlane(HarmonicPlane):
                    acceleration that won the cell (the one given first on a
                    tie; 0 where ``snr`` is -inf)
     ``accels``     the trial accelerations, float64 [nacc] (m/s^2)"""
+    whiten = None
 
     def __init__(self, snr, bin, nharm_log2, code, freq, df, nfft, nbin, kmin, cell, mean, std, plane, acc_index,
                  accels):
@@ -156,7 +157,7 @@ class AccelStage(PlaneStage):
         return out[:, :, :n]
 
     def accel_snr(self, plane, accels, nharm=16, cell=32, nfft=None, fmin=None, mean=None, std=None,
-                  stat_block=1024, max_bytes=1 << 30):
+                  stat_block=1024, max_bytes=1 << 30, whiten=None, zap=None):
         """:meth:`harmonic_snr` maximised over trial accelerations, on the
         device (extension: the reference has no counterpart).  Every trial is
         resampled in the time domain for every entry of ``accels`` [m/s^2]
@@ -177,10 +178,13 @@ class AccelStage(PlaneStage):
         its statistics are the trial's to that fraction.  ``accels`` must be
         finite, at least one, and within the limit of
         :meth:`accel_shift_step`.  ``accels = [0.0]`` gives the maps of
-        :meth:`harmonic_snr`.  No host synchronisation.  Returns an
-        :class:`AccelPlane`."""
+        :meth:`harmonic_snr`.  ``whiten`` / ``zap`` are those of
+        :meth:`harmonic_snr`: every chunk of spectra is whitened in place
+        straight after the transform and searched with a scale of ones
+        (``std`` is still reported but does not enter the normalisation).  No
+        host synchronisation.  Returns an :class:`AccelPlane`."""
         p = self._harmonic_plan(plane, nharm=nharm, cell=cell, nfft=nfft, fmin=fmin, mean=mean, std=std,
-                                stat_block=stat_block, max_bytes=max_bytes)
+                                stat_block=stat_block, max_bytes=max_bytes, whiten=whiten, zap=zap)
         ndm, T, ce, nbin, nu = p["ndm"], p["T"], p["cell"], p["nbin"], p["n_used"]
         acc, kap = self._accel_kappas(accels, plane.samprate, T, "accel_snr")
         na = acc.size
@@ -195,6 +199,10 @@ class AccelStage(PlaneStage):
         data, ld = self._plane_rows(plane.data)
         dev = data.device
         mean_d, std_d, scale32 = self._harmonic_stats(data, ld, p)
+        wplan = p["whiten"]
+        if wplan is not None:
+            edges_d, zap_d = self._whiten_tables(wplan, p["zap"], dev)
+            scale32 = torch.ones(ndm, dtype=torch.float32, device=dev)
         # chunks: whole trials with all their accelerations, or one trial and a block of accelerations
         nt_c, na_c = (min(ndm, rows // na), na) if rows >= na else (1, rows)
         chunks = [(lo, min(ndm, lo + nt_c), a0, min(na, a0 + na_c))
@@ -215,6 +223,7 @@ class AccelStage(PlaneStage):
         snr_c = torch.empty((mrows, out_ld), dtype=torch.float32, device=dev)
         code_c = torch.empty((mrows, out_ld), dtype=torch.int32, device=dev)
         work = torch.empty(mrows * nbin, dtype=torch.float32, device=dev) if p["nl"] > 3 else None
+        med = torch.empty((mrows, wplan.nblk), dtype=torch.float32, device=dev) if wplan is not None else None
         L = _lib.lib()
         r0 = 0
         for lo, hi, a0, a1 in chunks:
@@ -223,6 +232,8 @@ class AccelStage(PlaneStage):
             self._accel_launch(L, data, ndm, T, ld, src_d[r0:r0 + n], kap_d[r0:r0 + n],
                                mean32[lo:hi].repeat_interleave(nb), n, nu, y, y_ld)
             spec = torch.fft.rfft(y[:n, :nu], n=p["nfft"])
+            if wplan is not None:
+                self._whiten_rows(L, spec, nbin, wplan, edges_d, zap_d, med)
             rc = L.pss_harmonic_search(_engine.ptr(spec), n, nbin, int(spec.shape[1]),
                                        _engine.ptr(scale32[lo:hi].repeat_interleave(nb)), p["nl"], p["kmin"], ce,
                                        _engine.ptr(snr_c), _engine.ptr(code_c), out_ld, _engine.ptr(work),
@@ -244,12 +255,15 @@ class AccelStage(PlaneStage):
             r0 += n
         snr, code, bacc = best[:, :nq], bcode[:, :nq], bacc[:, :nq]
         k, lev, freq = self._decode_cells(code, ce, p["df"])
-        return AccelPlane(snr, k, lev, code, freq, p["df"], p["nfft"], nbin, p["kmin"], ce, mean_d, std_d, plane,
-                          bacc, acc)
+        cells = AccelPlane(snr, k, lev, code, freq, p["df"], p["nfft"], nbin, p["kmin"], ce, mean_d, std_d, plane,
+                           bacc, acc)
+        if wplan is not None:
+            cells.whiten = wplan
+        return cells
 
     def accel_search(self, plane, accels=None, amax=None, threshold=10.0, nharm=16, cell=32, dm_tol=1,
                      freq_tol=1.0, max_cells=1 << 20, nfft=None, fmin=None, mean=None, std=None, stat_block=1024,
-                     max_bytes=1 << 30, tol=1.0):
+                     max_bytes=1 << 30, tol=1.0, whiten=None, zap=None):
         """Acceleration search of a DM-time plane (extension: the reference has
         no counterpart): :meth:`accel_snr` over the trial accelerations, then
         the cells with ``snr >= threshold`` -- found on the device, only they
@@ -261,15 +275,16 @@ class AccelStage(PlaneStage):
         ``log_fap`` is still the single-trial false-alarm probability of
         :meth:`periodicity_search`: multiply the probability by the number of
         (trial, bin, level) searched and by the number of accelerations as
-        well.  Returns :class:`AccelCandidates`."""
+        well.  ``whiten`` / ``zap`` are those of :meth:`harmonic_snr`.
+        Returns :class:`AccelCandidates`."""
         if (accels is None) == (amax is None):
             raise ValueError("accel_search: give either accels or amax")
         p = self._harmonic_plan(plane, nharm, cell, nfft, fmin, threshold, dm_tol, freq_tol, max_cells, mean, std,
-                                stat_block, max_bytes)
+                                stat_block, max_bytes, None, whiten, zap)
         if accels is None:
             accels = self.accel_trials(p["T"], plane.samprate, amax, tol)
         cells = self.accel_snr(plane, accels, nharm=nharm, cell=cell, nfft=nfft, fmin=fmin, mean=mean, std=std,
-                               stat_block=stat_block, max_bytes=max_bytes)
+                               stat_block=stat_block, max_bytes=max_bytes, whiten=whiten, zap=zap)
         base, packed = self._period_cells("accel_search", plane, cells, p, cells.acc_index)
         arr = np.empty(base.size, dtype=ACCEL_DTYPE)
         for name in PERIOD_DTYPE.names:

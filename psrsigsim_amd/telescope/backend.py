@@ -15,15 +15,16 @@ from .periodicity import harmonic_log_fap, period_candidates_from_cells  # noqa:
 from .accel import AccelStage, AccelPlane, AccelCandidates, ACCEL_DTYPE, C_M_S  # noqa: F401
 from .fold_candidates import FoldStage, FoldedCandidates, fold_chi2, _fold_best  # noqa: F401
 from .rfi import RfiStage, RfiMask, inject_rfi  # noqa: F401
+from .whiten import WhitenStage, WhitenPlan  # noqa: F401
 from .ffa import FFAStage, FFAPlane, FFACandidates, FFA_DTYPE, ffa_candidates_from_cells  # noqa: F401
 
 __all__ = ['Backend', 'DedispersedPlane', 'BoxcarPlane', 'PulseCandidates', 'HarmonicPlane', 'PeriodCandidates',
            'FoldedCandidates', 'AccelPlane', 'AccelCandidates', 'RfiMask', 'inject_rfi', 'FFAPlane', 'FFACandidates',
-           'SubbandPlan']
+           'SubbandPlan', 'WhitenPlan']
 
 
-class Backend(ChannelizeStage, RfiStage, DedisperseStage, SubbandStage, PulseSearchStage, PeriodicityStage, AccelStage,
-              FoldStage, FFAStage):
+class Backend(ChannelizeStage, RfiStage, DedisperseStage, SubbandStage, PulseSearchStage, WhitenStage, PeriodicityStage,
+              AccelStage, FoldStage, FFAStage):
     def __init__(self, samprate=None, name=None):
         self._name = name
         self._samprate = make_quant(samprate, "MHz")

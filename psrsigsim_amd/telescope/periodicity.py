@@ -6,6 +6,7 @@ from .._units import to_value
 from .. import _engine, _lib
 from .plane import (PlaneStage, Candidates, cluster_cells, _cluster_candidates, _check_plane, _integers, _check_cells,
                     _threshold, _given_stats)
+from .whiten import WhitenStage
 
 
 class HarmonicPlane(object):
@@ -27,7 +28,10 @@ class HarmonicPlane(object):
     ``mean``       torch float64 [nDM], the baseline subtracted from each trial
     ``std``        torch float64 [nDM], the noise of one sample of each trial
                    (0: a trial without a usable variance, its power is 0)
-    ``plane``      the :class:`DedispersedPlane` that was searched"""
+    ``plane``      the :class:`DedispersedPlane` that was searched
+    ``whiten``     None, or the :class:`WhitenPlan` the spectrum was whitened
+                   with (``std`` then did not enter the normalisation)"""
+    whiten = None
 
     def __init__(self, snr, bin, nharm_log2, code, freq, df, nfft, nbin, kmin, cell, mean, std, plane):
         self.snr = snr
@@ -127,13 +131,16 @@ class PeriodicityStage(PlaneStage):
 
     @staticmethod
     def _harmonic_plan(plane, nharm=16, cell=32, nfft=None, fmin=None, threshold=10.0, dm_tol=1, freq_tol=1.0,
-                       max_cells=1 << 20, mean=None, std=None, stat_block=1024, max_bytes=1 << 30, spectrum=None):
+                       max_cells=1 << 20, mean=None, std=None, stat_block=1024, max_bytes=1 << 30, spectrum=None,
+                       whiten=None, zap=None):
         """Validate the arguments of :meth:`dm_spectrum`, :meth:`harmonic_snr`
         and :meth:`periodicity_search` on the host (nothing touches the
         device): returns a dict with ndm, T, nl (levels, log2(nharm) + 1), cell,
         nfft, nbin, n_used (samples of a trial that enter the transform), df
         (Hz), kmin, threshold, dm_tol, freq_tol, max_cells, mean, std (float64
-        [nDM] or None), stat_block and chunk (trials per spectrum chunk)."""
+        [nDM] or None), stat_block, chunk (trials per spectrum chunk), whiten
+        (the :class:`WhitenPlan`, or None for off) and zap (the mask, or
+        None)."""
         what = "periodicity search"
         ndm, T = _check_plane(what, plane, 2, "too small")
         nh, ce, sb, mc, mb, nf = _integers(what, "nharm, cell, nfft, stat_block, max_cells and max_bytes", nharm, cell,
@@ -173,9 +180,10 @@ class PeriodicityStage(PlaneStage):
             kmin = max(1, int(np.ceil(fm / df)))
         th = _threshold(what, threshold, dm_tol, "freq_tol", freq_tol)
         mean, std = _given_stats(what, mean, std, ndm)
+        wplan, zap = WhitenStage._whiten_args(what, whiten, zap, nbin)
         return dict(ndm=ndm, T=T, nl=nh.bit_length(), cell=ce, nfft=nf, nbin=nbin, n_used=min(T, nf), df=df,
                     kmin=kmin, threshold=th, dm_tol=dm_tol, freq_tol=freq_tol, max_cells=mc, mean=mean, std=std,
-                    stat_block=sb, chunk=max(1, min(ndm, mb // per_trial)))
+                    stat_block=sb, chunk=max(1, min(ndm, mb // per_trial)), whiten=wplan, zap=zap)
 
     def dm_spectrum(self, plane, nfft=None, mean=None, trials=None):
         """The complex spectrum of every trial of a DM-time plane on the
@@ -222,7 +230,7 @@ class PeriodicityStage(PlaneStage):
         return torch.fft.rfft(data[lo:hi, :n_used] - mean32[lo:hi, None], n=nfft)
 
     def harmonic_snr(self, plane, nharm=16, cell=32, nfft=None, fmin=None, mean=None, std=None, stat_block=1024,
-                     max_bytes=1 << 30, spectrum=None):
+                     max_bytes=1 << 30, spectrum=None, whiten=None, zap=None):
         """Incoherent harmonic sums of the power spectrum of a DM-time plane on
         the device (extension: the reference has no counterpart).  Every trial
         is transformed (:meth:`dm_spectrum`), its power normalised to unit mean
@@ -246,9 +254,24 @@ class PeriodicityStage(PlaneStage):
         spectrum stays within ``max_bytes`` (with 8 or 16 harmonics the
         kernel's power pass takes half as much again as workspace); the maps do
         not depend on the chunking.  ``spectrum`` (from :meth:`dm_spectrum`, all trials) skips
-        the transform.  No host synchronisation."""
+        the transform.
+
+        ``whiten`` (None / False: off; True: :meth:`whiten_plan` (nbin); a
+        :class:`WhitenPlan`; or a dict of :meth:`whiten_plan`'s keywords)
+        whitens every spectrum chunk in place straight after the transform
+        (:meth:`whiten_spectrum`: block medians of the power, red noise) and
+        hands the kernel a scale of ones: ``mean`` is used as before, ``std``
+        is still measured or taken and reported, but does not enter the
+        normalisation.  A caller's ``spectrum`` is whitened into a copy and
+        left alone: that path takes one more spectrum of all trials in device
+        memory, outside ``max_bytes`` (a spectrum that had to be converted to
+        contiguous complex64 is a copy already and is whitened in place).
+        ``zap`` (:meth:`zap_mask`, an array or a device tensor of
+        nbin entries) replaces the bins it sets by the neutral value of power
+        1; it needs ``whiten``.  The plan used is the result's ``whiten``.  No
+        host synchronisation."""
         p = self._harmonic_plan(plane, nharm=nharm, cell=cell, nfft=nfft, fmin=fmin, mean=mean, std=std,
-                                stat_block=stat_block, max_bytes=max_bytes, spectrum=spectrum)
+                                stat_block=stat_block, max_bytes=max_bytes, spectrum=spectrum, whiten=whiten, zap=zap)
         ndm, ce, nbin = p["ndm"], p["cell"], p["nbin"]
         data, ld = self._plane_rows(plane.data)
         mean_d, std_d, scale32 = self._harmonic_stats(data, ld, p)
@@ -263,6 +286,11 @@ class PeriodicityStage(PlaneStage):
                 spec_all = spec_all.to(torch.complex64).contiguous()
         L = _lib.lib()
         step = ndm if spectrum is not None else p["chunk"]
+        wplan = p["whiten"]
+        if wplan is not None:
+            edges_d, zap_d = self._whiten_tables(wplan, p["zap"], data.device)
+            med = torch.empty((step, wplan.nblk), dtype=torch.float32, device=data.device)
+            scale32 = torch.ones(ndm, dtype=torch.float32, device=data.device)
         # 8 and 16 harmonics: the kernel's power pass (half a spectrum chunk of workspace); below, gathering
         # from the spectrum itself is as fast or faster -- the same bits either way
         work = torch.empty(step * nbin, dtype=torch.float32, device=data.device) if p["nl"] > 3 else None
@@ -270,6 +298,10 @@ class PeriodicityStage(PlaneStage):
             hi = min(ndm, lo + step)
             spec = spec_all if spectrum is not None else self._spectrum_rows(data, mean32, lo, hi, p["n_used"],
                                                                              p["nfft"])
+            if wplan is not None:
+                # (the caller's own tensor is left alone; a converted copy of it is ours)
+                spec = self._whiten_rows(L, spec, nbin, wplan, edges_d, zap_d, med,
+                                         torch.empty_like(spec) if spec is spectrum else None)
             rc = L.pss_harmonic_search(_engine.ptr(spec), hi - lo, nbin, int(spec.shape[1]),
                                        _engine.ptr(scale32[lo:hi]), p["nl"], p["kmin"], ce, _engine.ptr(snr[lo:hi]),
                                        _engine.ptr(code[lo:hi]), out_ld, _engine.ptr(work), _engine.stream_ptr())
@@ -277,11 +309,14 @@ class PeriodicityStage(PlaneStage):
             del spec
         snr, code = snr[:, :nq], code[:, :nq]
         k, lev, freq = self._decode_cells(code, ce, p["df"])
-        return HarmonicPlane(snr, k, lev, code, freq, p["df"], p["nfft"], nbin, p["kmin"], ce, mean_d, std_d, plane)
+        cells = HarmonicPlane(snr, k, lev, code, freq, p["df"], p["nfft"], nbin, p["kmin"], ce, mean_d, std_d, plane)
+        if wplan is not None:
+            cells.whiten = wplan
+        return cells
 
     def periodicity_search(self, plane, threshold=10.0, nharm=16, cell=32, dm_tol=1, freq_tol=1.0,
                            max_cells=1 << 20, nfft=None, fmin=None, mean=None, std=None, stat_block=1024,
-                           max_bytes=1 << 30, spectrum=None):
+                           max_bytes=1 << 30, spectrum=None, whiten=None, zap=None):
         """Periodicity search of a DM-time plane (extension: the reference has
         no counterpart): :meth:`harmonic_snr`, then the cells with
         ``snr >= threshold`` -- found on the device, only they cross to the
@@ -302,12 +337,15 @@ class PeriodicityStage(PlaneStage):
         search's, and ``log_fap``, the logarithm of the single-trial
         false-alarm probability of each candidate from the chi-square
         distribution with 2 h degrees of freedom; multiply the probability by
-        the number of (trial, bin, level) searched.  Returns
+        the number of (trial, bin, level) searched.  ``whiten`` / ``zap`` are
+        those of :meth:`harmonic_snr`: on data with red noise or interference
+        lines the unwhitened search returns little else.  Returns
         :class:`PeriodCandidates`."""
         p = self._harmonic_plan(plane, nharm, cell, nfft, fmin, threshold, dm_tol, freq_tol, max_cells, mean, std,
-                                stat_block, max_bytes, spectrum)
+                                stat_block, max_bytes, spectrum, whiten, zap)
         cells = self.harmonic_snr(plane, nharm=nharm, cell=cell, nfft=nfft, fmin=fmin, mean=mean, std=std,
-                                  stat_block=stat_block, max_bytes=max_bytes, spectrum=spectrum)
+                                  stat_block=stat_block, max_bytes=max_bytes, spectrum=spectrum, whiten=whiten,
+                                  zap=zap)
         return PeriodCandidates(self._period_cells("periodicity_search", plane, cells, p)[0], cells, p["threshold"])
 
     def _period_cells(self, what, plane, cells, p, *maps):
