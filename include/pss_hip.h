@@ -869,6 +869,67 @@ int pss_ffa_profile_search(const float *prof, int32_t nser, int64_t n, int32_t p
                            const float *rm, int32_t nw, int32_t cell, float *snr, int32_t *code, int32_t *phase,
                            int64_t out_ld, void *stream);
 
+/*
+ * pss_toa_fit: pulse arrival times from folded profiles (extension, no
+ * reference counterpart): Taylor's (1992) Fourier-domain template match
+ * (FFTFIT) of every (channel, sub-integration) profile of a fold-mode signal.
+ * Profile (c, s), c < nchan, s < nsub, is the N = nbin floats data[c * ld +
+ * s * nbin ..): a fold-mode signal's own layout.  It is fitted as p[n] ~ a +
+ * b s((n / N) - tau) against the template t = c (ntmpl == nchan) or 0 (ntmpl
+ * == 1).  With the unnormalised transforms P_k = sum_n p_n e^{-2 pi i k n / N}
+ * and S_k likewise, the harmonics k = 1 .. K, K = min(nharm, (N - 1) / 2) (the
+ * Nyquist harmonic is never used), and the template table tspec[ntmpl][K + 1][2]
+ * float32 (planned in float64 on the host and rounded once) that holds
+ * (Re S_k, Im S_k) at k = 0 .. K (S_0 is needed for the offset a alone):
+ *   X_k     = P_k conj(S_k)
+ *   C(tau)  = sum_k Re[X_k e^{+2 pi i k tau}]        S2 = sum_k |S_k|^2
+ *   coarse  : j* = the first maximum of C on the grid tau_j = j / N, j < N
+ *   refine  : the root delta of C' in [-1 / N, 1 / N] around j* / N, by Newton
+ *             steps from delta = 0, delta' = delta - g / (2 pi D), g = sum_k k
+ *             Im[X_k e^{i phi_k}], D = sum_k k^2 Re[X_k e^{i phi_k}], kept
+ *             inside the bracket that the sign of g maintains (g < 0 raises the
+ *             lower end; a step of 2^-26 turns or more that leaves the bracket,
+ *             or D <= 0, bisects it).
+ *             The phase phi_k / 2 pi is ((k j*) mod N) / N, reduced in integers,
+ *             plus k delta, brought to [-1/2, 1/2] before the sine.  The
+ *             iteration stops at the delta whose step is below 2^-26 turns
+ *             (status 0) or after 24 evaluations (status 1).
+ *   tau     = j* / N + delta, in turns, wrapped to [-1/2, 1/2): positive when
+ *             the profile arrives later than the template
+ *   b       = C(tau) / S2                     a = (P_0 - b S_0) / N
+ *   R       = sum_k |P_k|^2 - C(tau)^2 / S2
+ *   sF2     = max(R, 0) / (2 K - 2), the variance of the real and of the
+ *             imaginary part of P_k; K = 1 leaves no degree of freedom: +inf
+ *   tau_err = sqrt(sF2 / (b D)) / 2 pi        b_err = sqrt(sF2 / S2)
+ *   rms     = sqrt(2 sF2 / N), the noise per bin      snr = b / b_err
+ *   out[(c * nsub + s) * out_ld + 0 .. 8) = tau, tau_err, b, b_err, a, rms, snr,
+ *             status
+ * status 2 is a degenerate fit: C(tau) <= 0 or D <= 0 (a constant profile among
+ * them: C = 0) gives tau = the coarse maximum, tau_err = b_err = +inf, snr =
+ * b / inf and the other fields by the formulas above; a profile with a
+ * non-finite sample gives tau = 0, both errors +inf and NaN in b, a, rms and
+ * snr.  A profile's bits depend on its own samples and its template only: not
+ * on the profiles beside it, their number, the alignment of data / ld / out /
+ * out_ld nor the run.  nbin = 2^m in [32, 4096] takes the FFT path (a profile
+ * is one complex sequence of N / 2 points: even and odd bins; a workgroup owns
+ * 8192 / nbin profiles and a group of min(64, nbin / 32) lanes refines one);
+ * every other nbin the direct path, O(K nbin) per profile with a workgroup
+ * each, in float64 sums rounded once.  On either path the sums run over p_n -
+ * p_0, which leaves the harmonics k >= 1 as they are and makes a constant
+ * profile exact zeros (P_0 gets N p_0 back), and sum |P_k|^2, S2 and C(tau) are
+ * float64 sums of float32 terms, R their float64 difference rounded once.  Both read data with 16-B loads where data is on the
+ * 16-B grid and ld and nbin are multiples of 4, with element loads otherwise.
+ * Nothing is read outside data[c * ld + 0 .. nsub * nbin) and the table,
+ * nothing is written outside out[r * out_ld + 0 .. 8).  No atomics, no
+ * workspace.
+ * PSS_EINVAL (nothing launched) on a NULL pointer, nchan < 1, nsub < 1, nbin
+ * outside [8, 8192], ld < nsub * nbin, out_ld < 8, ntmpl other than 1 or
+ * nchan, nharm < 1, and when the launch grid (nchan * nsub workgroups on the
+ * direct path, an 8192 / nbin-th of it on the FFT path) exceeds 2^31 - 1.
+ */
+int pss_toa_fit(const float *data, int32_t nchan, int32_t nsub, int32_t nbin, int64_t ld, const float *tspec,
+                int32_t ntmpl, int32_t nharm, float *out, int64_t out_ld, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

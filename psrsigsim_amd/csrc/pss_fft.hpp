@@ -439,7 +439,21 @@ __device__ __forceinline__ void tw16_fill(cf *tw16, int tid, int nthreads) {
     }
 }
 
-template <int L, int BATCH, int T, bool WAVE = false, int XRS = 1>
+// e^{2 pi i r}: the native sine and cosine (1.2e-7 absolute), or -- PRECISE --
+// sincospi, for a transform whose results are differenced afterwards (the
+// template match's residual)
+template <bool PRECISE>
+__device__ __forceinline__ cf tw_rev(float r) {
+    if constexpr (PRECISE) {
+        cf w;
+        sincospif(2.0f * r, &w.y, &w.x);
+        return w;
+    } else {
+        return expi_rev(r);
+    }
+}
+
+template <int L, int BATCH, int T, bool WAVE = false, int XRS = 1, bool PRECISE = false>
 struct Fft {
     using LD = Lds<L, XRS>;
     // byte-address forms of the exchanges (see lds_byte)
@@ -531,7 +545,7 @@ struct Fft {
                 cf w[H];
                 const float base = (float)k * (1.0f / (float)(Ns * R));   // [0, 1/R)
 #pragma unroll
-                for (int p2 = 1; p2 < H; p2 *= 2) w[p2] = expi_rev(INV ? p2 * base : -p2 * base);
+                for (int p2 = 1; p2 < H; p2 *= 2) w[p2] = tw_rev<PRECISE>(INV ? p2 * base : -p2 * base);
 #pragma unroll
                 for (int q = 3; q < H; ++q) {
                     const int hi = 1 << (31 - __builtin_clz(q));   // compile-time after unrolling
@@ -540,7 +554,7 @@ struct Fft {
 #pragma unroll
                 for (int q = 1; q < H; ++q) a[q] = cmul(a[q], w[q]);
                 if constexpr (H < R) {
-                    const cf wh = expi_rev(INV ? H * base : -H * base);
+                    const cf wh = tw_rev<PRECISE>(INV ? H * base : -H * base);
                     a[H] = cmul(a[H], wh);
 #pragma unroll
                     for (int q = 1; q < H; ++q) a[H + q] = cmul(a[H + q], cmul(wh, w[q]));

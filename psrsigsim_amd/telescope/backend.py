@@ -17,14 +17,15 @@ from .fold_candidates import FoldStage, FoldedCandidates, fold_chi2, _fold_best 
 from .rfi import RfiStage, RfiMask, inject_rfi  # noqa: F401
 from .whiten import WhitenStage, WhitenPlan  # noqa: F401
 from .ffa import FFAStage, FFAPlane, FFACandidates, FFA_DTYPE, ffa_candidates_from_cells  # noqa: F401
+from .toa import TOAStage, TOATemplate, TOAs  # noqa: F401
 
 __all__ = ['Backend', 'DedispersedPlane', 'BoxcarPlane', 'PulseCandidates', 'HarmonicPlane', 'PeriodCandidates',
            'FoldedCandidates', 'AccelPlane', 'AccelCandidates', 'RfiMask', 'inject_rfi', 'FFAPlane', 'FFACandidates',
-           'SubbandPlan', 'WhitenPlan']
+           'SubbandPlan', 'WhitenPlan', 'TOATemplate', 'TOAs']
 
 
 class Backend(ChannelizeStage, RfiStage, DedisperseStage, SubbandStage, PulseSearchStage, WhitenStage, PeriodicityStage,
-              AccelStage, FoldStage, FFAStage):
+              AccelStage, FoldStage, FFAStage, TOAStage):
     def __init__(self, samprate=None, name=None):
         self._name = name
         self._samprate = make_quant(samprate, "MHz")
