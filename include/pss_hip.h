@@ -930,6 +930,104 @@ int pss_ffa_profile_search(const float *prof, int32_t nser, int64_t n, int32_t p
 int pss_toa_fit(const float *data, int32_t nchan, int32_t nsub, int32_t nbin, int64_t ld, const float *tspec,
                 int32_t ntmpl, int32_t nharm, float *out, int64_t out_ld, void *stream);
 
+/*
+ * pss_toa_wide_fit: wideband arrival times (extension, no reference
+ * counterpart): one phase and one DM per sub-integration, fitted to all its
+ * channels at once (Pennucci, Demorest & Ransom 2014), where pss_toa_fit fits
+ * every profile on its own.  data, nchan, nsub, nbin, ld, tspec, ntmpl and
+ * nharm are those of pss_toa_fit, and so are N, K, P_k, S_k, X_nk = P_nk
+ * conj(S_nk), PP_n = sum_k |P_nk|^2 and S2_n = sum_k |S_nk|^2 of channel n
+ * (the same device code forms them, on the same two paths).  Further inputs:
+ *   kappa[nchan]  float64: turns of phase per unit of DM, DM_K nu_n^-2 / P
+ *   phi0[nchan]   float64: the phase predicted for channel n at the nominal
+ *                 DM, reduced to [-1/2, 1/2) on the host
+ *   wt[nchan][nsub] float32: 1 / sigma_F^2, the inverse variance of the real
+ *                 and of the imaginary part of P_k.  A weight <= 0 or
+ *                 non-finite leaves the profile out, and so does a non-finite
+ *                 sample in it.  The usable channels of a sub-integration are
+ *                 the rest, in index order; every sum over n below runs over
+ *                 them alone.
+ *   ndm (odd, >= 1), dm_step (>= 0): the coarse grid d_i = i dm_step, |i| <=
+ *                 ndm / 2, around the nominal DM (d = 0).
+ * For every sub-integration:
+ *   phi_n   = phi0_n + phi + kappa_n d
+ *   C_n     = sum_k Re[X_nk e^{2 pi i k phi_n}]
+ *   F       = sum_n (wt_n / S2_n) C_n^2      (the amplitudes b_n = C_n / S2_n
+ *             are profiled out), maximised over (phi, d).
+ *   phase   : phi_n is formed and reduced by rint in float64; k phi_n is
+ *             formed in float64, reduced by rint and rounded once to float32
+ *             for sincospif.  The terms of a harmonic sum are float32
+ *             products, their sums float64; everything per channel and above
+ *             is float64, the state (phi, d) included.
+ *   coarse  : for every d_i, Xbar_k = sum_n wt_n X_nk e^{2 pi i k (phi0_n +
+ *             kappa_n d_i)} (channels in index order, float64 sums of float32
+ *             terms, rounded once to float32), c_j = sum_k Re[Xbar_k e^{2 pi i
+ *             k j / N}], j < N, by float64 sums rounded once to float32 (at
+ *             every N), and its first maximum j*(i).  The start is the (d_i,
+ *             j* / N wrapped to [-1/2, 1/2)) of the largest value: ties to the
+ *             lower |i|, then the lower i, then the lower j.
+ *   refine  : with g_n = sum_k k Im[.], D_n = sum_k k^2 Re[.], w_n = wt_n /
+ *             S2_n, C'_n = -2 pi g_n, C''_n = -4 pi^2 D_n, q_n = 2 w_n C_n C'_n,
+ *             h_n = 2 w_n (C'_n^2 + C_n C''_n): the gradient is (sum q_n, sum
+ *             kappa_n q_n), the Hessian H = [[sum h_n, sum kappa_n h_n], [.,
+ *             sum kappa_n^2 h_n]], the expected curvature E the same with e_n =
+ *             -8 pi^2 w_n C_n^2 T2_n / S2_n, T2_n = sum_k k^2 |S_nk|^2, for
+ *             h_n.  The step from a point is p = -H^-1 grad where H is
+ *             negative definite (H_11 < 0, det H > 0), else -E^-1 grad, else 0;
+ *             it is scaled down so that max(|p_phi|, |p_d| kspan) <= 4 / N (four
+ *             bins), kspan = max_n |kappa_n - mean kappa|.  The first
+ *             evaluation is at the start.  A trial point x + p is accepted
+ *             when |grad(x + p) . p| <= |grad(x) . p|, and a new step is taken
+ *             from it; otherwise p is halved.  Values of F are never compared.
+ *             When the step to try next has |p_phi| < 2^-26 and |p_d| kspan <
+ *             2^-26 turns the fit has converged (status 0): that last step is
+ *             taken without an evaluation.  Status 1 after 32 evaluations.
+ *   status 2: fewer than two usable channels or kspan = 0 ((phi, d) is the
+ *             coarse start, no evaluation), or -H / 2 at the solution not
+ *             positive definite: phi_err = d_err = +inf, cov = 0.
+ *   out[s * out_ld + 0 .. 10), float64: phi wrapped to [-1/2, 1/2), referred
+ *             to infinite frequency; phi_err; d; d_err; cov(phi, d) -- (phi_err^2,
+ *             cov; cov, d_err^2) is the inverse of -H / 2 at the solution;
+ *             chi2 = sum_n wt_n (PP_n - C_n^2 / S2_n); dof = 2 K n_used - n_used
+ *             - 2; n_used; evaluations; status.
+ *   prof[(c * nsub + s) * prof_ld + 0 .. 4), float32: b_n, b_err_n = sqrt(1 /
+ *             (wt_n S2_n)), the channel's chi2 term, 1 -- or, for a profile
+ *             left out, (0, or NaN with a non-finite sample), +inf, 0, 0.
+ * A sub-integration's bits depend on its own usable profiles, their entries of
+ * the tables and the grid alone: not on nsub, the other sub-integrations, the
+ * channels left out (the fit without them gives the same bits), the alignment
+ * or strides, nor the run.  Channels are added in blocks of 4 (K > 32), 16 (K >
+ * 8) or 64 usable channels, in order, and the blocks in order.  No atomics, no
+ * host synchronisation between the launches.  All intermediate storage is
+ * work[0 .. pss_toa_wide_workspace_bytes(nchan, nsub, nbin, nharm, ndm)), on
+ * the 16-byte grid (0 for arguments pss_toa_wide_fit rejects): X_nk as float2
+ * [nsub][nchan][K], the sums of every profile, the channel lists, Xbar_k of
+ * every trial, the trials' maxima,
+ * the partial sums and the state.
+ * PSS_EINVAL (nothing launched) on a NULL pointer, nchan < 1, nsub < 1, nbin
+ * outside [8, 8192], ld < nsub * nbin, out_ld < 10, prof_ld < 4, ntmpl other
+ * than 1 or nchan, nharm < 1, ndm even or < 1, dm_step negative or non-finite,
+ * work_bytes too small, work off the 16-byte grid, and a launch grid above
+ * 2^31 - 1.
+ */
+int64_t pss_toa_wide_workspace_bytes(int32_t nchan, int32_t nsub, int32_t nbin, int32_t nharm, int32_t ndm);
+int pss_toa_wide_fit(const float *data, int32_t nchan, int32_t nsub, int32_t nbin, int64_t ld, const float *tspec,
+                     int32_t ntmpl, int32_t nharm, const double *kappa, const double *phi0, const float *wt,
+                     int32_t ndm, double dm_step, double *out, int64_t out_ld, float *prof, int64_t prof_ld,
+                     void *work, int64_t work_bytes, void *stream);
+/*
+ * pss_toa_wide_stages: the stages first .. last of pss_toa_wide_fit alone, 0
+ * <= first <= last <= 3, for timing them (tools/toa_wide_bench.py): 0 the
+ * spectra, 1 the channel lists, the coarse trials and the start, 2 the 32
+ * rounds of evaluation and step, 3 the final evaluation and the outputs.  The
+ * arguments and their checks are those of pss_toa_wide_fit, which is the
+ * stages 0 .. 3; a stage reads what the stages before it left in work.
+ */
+int pss_toa_wide_stages(const float *data, int32_t nchan, int32_t nsub, int32_t nbin, int64_t ld, const float *tspec,
+                        int32_t ntmpl, int32_t nharm, const double *kappa, const double *phi0, const float *wt,
+                        int32_t ndm, double dm_step, double *out, int64_t out_ld, float *prof, int64_t prof_ld,
+                        void *work, int64_t work_bytes, int32_t first, int32_t last, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -100,6 +100,11 @@ EXPORTS = {
     "pss_ffa_profile_search": (ctypes.c_int, [c_vp, c_i32, c_i64, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp,
                                               c_vp, c_i64, c_vp]),
     "pss_toa_fit": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i64, c_vp, c_i32, c_i32, c_vp, c_i64, c_vp]),
+    "pss_toa_wide_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_i32, c_i32]),
+    "pss_toa_wide_fit": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32,
+                                        ctypes.c_double, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "pss_toa_wide_stages": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32,
+                                           ctypes.c_double, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_vp]),
     "pss_host_pchip_coef": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, ctypes.c_int]),
     "pss_host_ppoly_eval": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, ctypes.c_int]),
     "pss_host_pchip_eval": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, ctypes.c_double, c_vp,

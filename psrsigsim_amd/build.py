@@ -22,7 +22,7 @@ UNITS = ["pss_pipeline.hip", "pss_fourstep.hip", "pss_fourstep_b.hip", "pss_smoo
          "pss_smooth_c.hip", "pss_single.hip", "pss_fallback.hip", "pss_searchout.hip", "pss_channelize.hip",
          "pss_dedisperse.hip", "pss_boxsearch.hip", "pss_harmsum.hip", "pss_foldseries.hip", "pss_accel.hip",
          "pss_rficlean.hip", "pss_ffa.hip", "pss_searchin.hip", "pss_whiten.hip",
-         "pss_toa.hip"]
+         "pss_toa.hip", "pss_toa_wide.hip"]
 SRC = [os.path.join(HERE, "csrc", u) for u in UNITS] + [os.path.join(HERE, "csrc", "pss_host.cpp")]
 # every header of csrc/ is hashed (a new one cannot be forgotten)
 DEPS = SRC + sorted(glob.glob(os.path.join(HERE, "csrc", "*.hpp"))) + [os.path.join(ROOT, "include", "pss_hip.h")]

@@ -17,11 +17,11 @@ from .fold_candidates import FoldStage, FoldedCandidates, fold_chi2, _fold_best 
 from .rfi import RfiStage, RfiMask, inject_rfi  # noqa: F401
 from .whiten import WhitenStage, WhitenPlan  # noqa: F401
 from .ffa import FFAStage, FFAPlane, FFACandidates, FFA_DTYPE, ffa_candidates_from_cells  # noqa: F401
-from .toa import TOAStage, TOATemplate, TOAs  # noqa: F401
+from .toa import TOAStage, TOATemplate, TOAs, WidebandTOAs  # noqa: F401
 
 __all__ = ['Backend', 'DedispersedPlane', 'BoxcarPlane', 'PulseCandidates', 'HarmonicPlane', 'PeriodCandidates',
            'FoldedCandidates', 'AccelPlane', 'AccelCandidates', 'RfiMask', 'inject_rfi', 'FFAPlane', 'FFACandidates',
-           'SubbandPlan', 'WhitenPlan', 'TOATemplate', 'TOAs']
+           'SubbandPlan', 'WhitenPlan', 'TOATemplate', 'TOAs', 'WidebandTOAs']
 
 
 class Backend(ChannelizeStage, RfiStage, DedisperseStage, SubbandStage, PulseSearchStage, WhitenStage, PeriodicityStage,
