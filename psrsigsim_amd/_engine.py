@@ -200,6 +200,14 @@ def ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def row_stride(t):
+    """The row pitch (elements) the library gets for a [rows, N] tensor of
+    dense rows: max(stride(0), N).  The stride torch reports for a one-row
+    tensor is arbitrary (``torch.empty(N, 1).t()`` has stride(0) == 1), and no
+    row is read past it there."""
+    return max(int(t.stride(0)), int(t.shape[1]))
+
+
 def ramp_words(samples, N):
     """frac(s/N) * 2^64 as uint64 (bin k gets exp(-2 pi i k s / N))."""
     x = np.asarray(samples, dtype=np.float64) / float(N)
@@ -335,7 +343,7 @@ def build_pipeline(sig, pend, rows, chan0, data, out=None, ws_role="main"):
     for k, v in P.items():
         if k != "arrays":
             setattr(p, k, v)
-    p.ld = data.stride(0)
+    p.ld = row_stride(data)
     p.data = ptr(data)
     src = pend.source
     if src is not None:
@@ -445,7 +453,7 @@ def filter_rows(sig, htab):
     h = to_dev(np.ascontiguousarray(np.asarray(htab, dtype=np.complex64)).view(np.float32))
     L = _lib.load()
     ws = workspace(L.pss_filter_workspace_bytes(rows, N))
-    rc = _lib.lib().pss_filter_rows(ptr(data), rows, N, data.stride(0), ptr(h), ptr(ws), stream_ptr())
+    rc = _lib.lib().pss_filter_rows(ptr(data), rows, N, row_stride(data), ptr(h), ptr(ws), stream_ptr())
     _lib.check(rc, "filter_rows")
 
 
@@ -458,7 +466,11 @@ def null_shift_device(sig, pend, count):
     replayed for global channels 0..1 (the pairing the full run uses, so the
     values are bit-identical to the final channel 0) from the source when it
     is generated, else taken from the local buffer or the channel-0 shadow --
-    on any shard, without communication."""
+    on any shard, without communication.
+
+    A signal shorter than ``count`` samples (less than one period) is scanned
+    to its end, as the reference's slice ``data[0, :Nph]`` is: the scan stops
+    at the row's N samples and the shift keeps count//2."""
     N = sig._ncols
     nrow = min(2, sig.Nchan)
     if sig._c0 == 0 and sig._c1 >= nrow and sig._buf is not None:
@@ -483,8 +495,11 @@ def null_shift_device(sig, pend, count):
         run(p, keep)
         row = scratch[0]
     out = torch.empty(2, dtype=torch.int64, device=device())
-    rc = _lib.lib().pss_null_shift(ptr(row), int(count), ptr(out), stream_ptr())
+    scan = min(int(count), N)
+    rc = _lib.lib().pss_null_shift(ptr(row), scan, ptr(out), stream_ptr())
     _lib.check(rc, "null_shift")
+    if scan != int(count):
+        out[0] += int(count) // 2 - scan // 2                # (pss_null_shift wrote scan // 2 - argmax)
     return out
 
 

@@ -59,7 +59,7 @@ class Backend(ChannelizeStage, RfiStage, DedisperseStage, SubbandStage, PulseSea
             raise ValueError("cannot reshape array of size %d into shape (%d,%d,%d)"
                              % (Nf * max(width, 0), Nf, N_fold, Npbins // 2))
         out = torch.empty((Nf, Npbins // 2), dtype=torch.float32, device=data.device)
-        rc = _lib.lib().pss_fold(_engine.ptr(data), _engine.ptr(out), Nf, data.stride(0), Npbins,
+        rc = _lib.lib().pss_fold(_engine.ptr(data), _engine.ptr(out), Nf, _engine.row_stride(data), Npbins,
                                  N_fold, _engine.stream_ptr())
         _lib.check(rc, "fold")
         return out
@@ -80,7 +80,7 @@ class Backend(ChannelizeStage, RfiStage, DedisperseStage, SubbandStage, PulseSea
         if nbin < 1 or nper < 1:
             raise ValueError("fold_periods: %d samples hold no whole period of %d bins" % (Nt, nbin))
         out = torch.empty((Nf, nbin), dtype=torch.float32, device=data.device)
-        rc = _lib.lib().pss_fold_periods(_engine.ptr(data), _engine.ptr(out), Nf, data.stride(0), nbin, nper,
+        rc = _lib.lib().pss_fold_periods(_engine.ptr(data), _engine.ptr(out), Nf, _engine.row_stride(data), nbin, nper,
                                          _engine.stream_ptr())
         _lib.check(rc, "fold_periods")
         return out

@@ -195,7 +195,7 @@ class PlaneStage(object):
     def _plane_rows(data):
         if data.dtype != torch.float32 or data.stride(1) != 1:
             data = data.to(torch.float32).contiguous()
-        return data, max(int(data.stride(0)), int(data.shape[1]))
+        return data, _engine.row_stride(data)
 
     @staticmethod
     def _trial_stats(data, ld, stat_block):

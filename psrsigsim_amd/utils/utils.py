@@ -49,7 +49,7 @@ def shift_t(y, shift, dt=1):
     ramp = _engine.u64_to_i64_tensor(_engine.ramp_words(s, N))
     nyq = _engine.to_dev(np.cos(np.pi * s).astype(np.float32))
     ws = _engine.workspace(_lib.load().pss_workspace_bytes(R, N))
-    rc = _lib.lib().pss_shift_rows(_engine.ptr(t), R, N, t.stride(0), _engine.ptr(ramp),
+    rc = _lib.lib().pss_shift_rows(_engine.ptr(t), R, N, _engine.row_stride(t), _engine.ptr(ramp),
                                    _engine.ptr(nyq), _engine.ptr(ws), _engine.stream_ptr())
     _lib.check(rc, "shift_t")
     if N % 2:
@@ -66,7 +66,7 @@ def down_sample(ar, fact):
     if N % fact:
         raise ValueError("cannot reshape array of size %d into shape (%d)" % (N, fact))
     out = torch.empty((R, N // fact), dtype=torch.float32, device=t.device)
-    rc = _lib.lib().pss_down_sample(_engine.ptr(t), _engine.ptr(out), R, N, t.stride(0), int(fact),
+    rc = _lib.lib().pss_down_sample(_engine.ptr(t), _engine.ptr(out), R, N, _engine.row_stride(t), int(fact),
                                     _engine.stream_ptr())
     _lib.check(rc, "down_sample")
     return _ret(out, was_np, was_1d)
@@ -90,7 +90,7 @@ def rebin(ar, newlen):
     lo, hi = rebin_edges(N, newlen)
     dlo, dhi = _engine.to_dev(lo), _engine.to_dev(hi)
     out = torch.empty((R, newlen), dtype=torch.float32, device=t.device)
-    rc = _lib.lib().pss_rebin(_engine.ptr(t), _engine.ptr(out), R, N, t.stride(0), int(newlen),
+    rc = _lib.lib().pss_rebin(_engine.ptr(t), _engine.ptr(out), R, N, _engine.row_stride(t), int(newlen),
                               _engine.ptr(dlo), _engine.ptr(dhi), _engine.stream_ptr())
     _lib.check(rc, "rebin")
     return _ret(out, was_np, was_1d)

@@ -3,8 +3,9 @@ search, periodicity, acceleration, candidate fold, channeliser).
 
 The kernel tests give a kernel views inside larger tensors whose every other
 word holds a sentinel: ``GuardedInput`` (a stray read meets the sentinel and
-lands in a result) and ``GuardedOutput`` (``read`` asserts that nothing but
-the valid part of every row was written).  These guard checks are the only
+lands in a result), ``GuardedOutput`` (``read`` asserts that nothing but
+the valid part of every row was written) and ``GuardedRows`` (both, for rows
+that a kernel updates in place).  These guard checks are the only
 evidence that a kernel stays inside its rows, so there is one implementation,
 and tests/test_kernel_harness.py runs it on the CPU against a fake kernel.
 
@@ -46,6 +47,40 @@ class GuardedInput(object):
         self.view[:, :valid] = torch.from_numpy(values).to(device)
         self.ptr = self.view.data_ptr()
         self.base = self.parent.data_ptr() // 4 + lead
+        self.guard, self.shape, self.ld = guard, values.shape, ld
+        # the parent's regions in order (name, words); "rows" is the view
+        self.regions = (("the lead pad", pad), ("the guard rows before", guard_rows * row), ("the in_off slack", in_off),
+                        ("rows", rows * row), ("the guard rows after", guard_rows * row), ("the tail pad", pad))
+
+
+class GuardedRows(GuardedInput):
+    """A ``GuardedInput`` whose rows a kernel updates in place: ``rows`` is the
+    device view [rows][valid] the kernel gets (stride ``ld``), and ``read``
+    says afterwards that the kernel stayed inside it."""
+
+    @property
+    def rows(self):
+        return self.view[:, :self.shape[1]]
+
+    def read(self):
+        """A host copy of the valid part [rows][valid], after asserting that
+        every other word of the parent still holds the guard: the lead pad, the
+        guard rows before and after, the in_off slack, the columns [valid, ld)
+        of every row and the tail pad."""
+        o = self.parent.cpu().numpy()
+        at = 0
+        for name, words in self.regions:
+            part = o[at:at + words]
+            at += words
+            if name != "rows":
+                assert (part == self.guard).all(), "written in %s" % name
+                continue
+            body = part.reshape((self.shape[0], self.ld) + self.shape[2:])
+            bad = np.argwhere(body[:, self.shape[1]:] != self.guard)
+            assert not bad.size, "written in the pad columns [%d, %d) of row %d" % (self.shape[1], self.ld, bad[0][0])
+            got = body[:, :self.shape[1]].copy()
+        assert at == o.size
+        return got
 
 
 class GuardedOutput(object):

@@ -36,20 +36,27 @@ def test_shift_t_rows_every_geometry(N, hip_lib):
 # ---------------------------------------------------------------------------
 # (b) search-mode fast passes == generic
 # ---------------------------------------------------------------------------
-def _search_run(N, nchan, null):
+def _search_signal(N, nchan, null, dtype=np.float32, period=0.005):
+    """(signal, pulsar) with make_pulses, disperse and (``null``) a delayed
+    null pending: nothing has run yet, and observe() is the caller's."""
     import psrsigsim_amd as pss
     from psrsigsim_amd.signal import FilterBankSignal
     from psrsigsim_amd.pulsar import Pulsar, GaussProfile
     from psrsigsim_amd.ism import ISM
-    from psrsigsim_amd.telescope import telescope as T
     pss.seed(31)
-    sig = FilterBankSignal(1400, 400, Nsubband=nchan, fold=False)
-    psr = Pulsar(0.005, 1.0, profiles=GaussProfile(0.5, 0.05, 1))
+    sig = FilterBankSignal(1400, 400, Nsubband=nchan, fold=False, dtype=dtype)
+    psr = Pulsar(period, 1.0, profiles=GaussProfile(0.5, 0.05, 1))
     psr.make_pulses(sig, tobs=(N + 0.5) * 20.48e-6)
     assert sig.nsamp == N
     ISM().disperse(sig, 100)
     if null:
         psr.null(sig, 0.2)
+    return sig, psr
+
+
+def _search_run(N, nchan, null):
+    from psrsigsim_amd.telescope import telescope as T
+    sig, psr = _search_signal(N, nchan, null)
     T.Arecibo().observe(sig, psr, system="Lband_PUPPI", noise=True)
     return sig.data.cpu().numpy()
 
@@ -103,12 +110,12 @@ def test_search_fast_mask_table_forked_before_pass_a(hip_lib):
 # ---------------------------------------------------------------------------
 # (c) fold-mode fast passes == generic
 # ---------------------------------------------------------------------------
-def _fold_run(nchan, shard, nsub, bins):
+def _fold_signal(nchan, shard, nsub, bins):
+    """(signal, pulsar) of the fold-mode chain with make_pulses and disperse pending."""
     import psrsigsim_amd as pss
     from psrsigsim_amd.signal import FilterBankSignal
     from psrsigsim_amd.pulsar import Pulsar, GaussProfile
     from psrsigsim_amd.ism import ISM
-    from psrsigsim_amd.telescope import telescope as T
     pss.seed(37)
     sig = FilterBankSignal(1400, 400, Nsubband=nchan, sample_rate=F0_B1855 * bins * 1e-6, sublen=60.0,
                            fold=True, shard=shard)
@@ -119,6 +126,12 @@ def _fold_run(nchan, shard, nsub, bins):
     # 60 x 8192 and 30 x 2048; the caller checks the shape and the plan line)
     assert sig._ncols == nsub * bins
     ISM().disperse(sig, 13.299393)
+    return sig, psr
+
+
+def _fold_run(nchan, shard, nsub, bins):
+    from psrsigsim_amd.telescope import telescope as T
+    sig, psr = _fold_signal(nchan, shard, nsub, bins)
     T.Arecibo().observe(sig, psr, system="Lband_PUPPI", noise=True)
     return sig.data.cpu().numpy()
 

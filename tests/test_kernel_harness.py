@@ -108,6 +108,78 @@ def test_input_view_sits_where_asked_between_guards(shape, in_off, guard_rows, p
     assert (p == guard).sum() == p.size and p.size - vals.size >= 2 * (pad + guard_rows * ld * width)
 
 
+IN_LD = 13
+# (guard_rows, pad) of the in-place rows: the kernel tests' padding with and
+# without guard rows, and a pad of 5 whole rows
+IN_PLACE = [(0, kh.IN_PAD), (2, kh.IN_PAD), (2, 5 * IN_LD)]
+
+
+def _rows_in_place(shape, in_off, guard_rows, pad):
+    vals = np.random.default_rng(2).standard_normal(shape).astype(np.float32)
+    return vals, kh.GuardedRows(vals, IN_LD, in_off=in_off, guard=float(1 << 20), guard_rows=guard_rows, pad=pad,
+                                device="cpu")
+
+
+def fake_in_place_kernel(g):
+    """Doubles the valid part of every row, as an in-place kernel that stays in bounds does."""
+    g.rows.mul_(2.0)
+
+
+def _stray_in_place(g, where, width):
+    """An index into the parent of ``g`` inside the named region (None where the layout has no such region)."""
+    sizes = dict(g.regions)
+    start = dict(zip([n for n, _ in g.regions], np.cumsum([0] + [w for _, w in g.regions])))
+    row = IN_LD * width
+    if where == "the first pad column of the first row":
+        return int(start["rows"]) + VALID * width
+    if where == "the last pad column of the last row":
+        return int(start["rows"]) + ROWS * row - 1
+    name, end = where
+    if not sizes[name]:
+        return None
+    return int(start[name]) + (sizes[name] - 1 if end == "last" else 0)
+
+
+STRAY_IN_PLACE = ["the first pad column of the first row", "the last pad column of the last row"] + [
+    (name, end) for name in ("the lead pad", "the guard rows before", "the in_off slack", "the guard rows after",
+                             "the tail pad") for end in ("first", "last")]
+
+
+@pytest.mark.parametrize("guard_rows,pad", IN_PLACE)
+@pytest.mark.parametrize("in_off", [0, 1, 2, 3])
+@pytest.mark.parametrize("shape", [(ROWS, VALID), (ROWS, VALID, 2)], ids=["real", "complex"])
+def test_in_place_clean_write_passes_and_returns_the_valid_part(shape, in_off, guard_rows, pad):
+    vals, g = _rows_in_place(shape, in_off, guard_rows, pad)
+    assert tuple(g.rows.shape) == shape and g.rows.data_ptr() == g.ptr and g.rows.stride(0) == g.view.stride(0)
+    assert sum(w for _, w in g.regions) == g.parent.numel()
+    assert np.array_equal(g.read(), vals)                    # nothing written yet
+    fake_in_place_kernel(g)
+    got = g.read()
+    assert got.dtype == np.float32 and np.array_equal(got, 2 * vals)
+    got[0, 0] = 0                                            # a copy: the parent is left alone
+    assert np.array_equal(g.read(), 2 * vals)
+
+
+@pytest.mark.parametrize("where", STRAY_IN_PLACE, ids=lambda w: w if isinstance(w, str) else "%s word of %s" % (w[1], w[0]))
+@pytest.mark.parametrize("guard_rows,pad", IN_PLACE)
+@pytest.mark.parametrize("in_off", [0, 1, 2, 3])
+@pytest.mark.parametrize("shape", [(ROWS, VALID), (ROWS, VALID, 2)], ids=["real", "complex"])
+def test_in_place_one_stray_word_fails_read_and_names_the_region(shape, in_off, guard_rows, pad, where):
+    vals, g = _rows_in_place(shape, in_off, guard_rows, pad)
+    fake_in_place_kernel(g)
+    index = _stray_in_place(g, where, len(shape) - 1)
+    if index is None:
+        # (no guard rows, or in_off = 0: the region is empty in this layout and the clean read stands)
+        assert np.array_equal(g.read(), 2 * vals)
+        return
+    g.parent[index] = 1
+    with pytest.raises(AssertionError) as err:
+        g.read()
+    assert ("pad columns" if isinstance(where, str) else where[0]) in str(err.value), str(err.value)
+    g.parent[index] = float(1 << 20)                         # the guard put back: that word alone failed it
+    assert np.array_equal(g.read(), 2 * vals)
+
+
 def test_small_pieces():
     a = np.array([0.0, -0.0, np.nan], dtype=np.float32)
     assert kh.same_bits(a, a.copy()) and not kh.same_bits(a, np.array([0.0, 0.0, np.nan], dtype=np.float32))
