@@ -398,6 +398,7 @@ int pss_plan_geometry(int64_t nsamp, int32_t variant, int64_t *n1, int64_t *n2) 
 }
 
 static int run_paths(const PssPipeline *p, hipStream_t st);
+static int run_geometry(KP &k, int geom, hipStream_t st, float *row);
 
 int pss_run(const PssPipeline *p, void *stream) {
     int rc = validate(p);
@@ -439,7 +440,35 @@ static int run_paths(const PssPipeline *p, hipStream_t st) {
             row = const_cast<float *>(p->inj_box);
         }
     }
-    switch (plan_geometry(N, plan_variant(*p))) {
+    const int geom = plan_geometry(N, plan_variant(k.p));
+    if (geom != PSS_PLAN_FOURSTEP && p->null_mode == PSS_NULL_DELAYED && p->data_in_fft &&
+        p->src != PSS_SRC_FOLD) {
+        // Off the mask-table four-step a delayed null's mask rides in the
+        // imaginary part of the data's transform, whose fp32 error is relative
+        // to the larger of the two.  A fold-mode row (chi2(Nfold) draws) is
+        // as large as its mask (chi2(max(100, Nfold))); a search-mode row
+        // (chi2(1) draws x a profile <= 1, a few units at its peak) is 20-100
+        // times smaller, and came out at 1.3e-5 .. 3.4e-4 of its own maximum
+        // (N = 32 .. 512, tests/test_gpu_single_batched.py) against 3e-7 for
+        // the same chain run stage by stage.  So the data are delayed alone
+        // first (no null, copy or noise: the plain delay's kernels), then the
+        // mask alone, its epilogue loading the delayed data -- the two runs a
+        // stage-by-stage chain makes.
+        KP d = k;
+        d.p.null_mode = PSS_NULL_NONE;
+        d.p.noise = 0;
+        d.p.out_kind = PSS_OUT_NONE;
+        d.p.out_len = 0;
+        const int rc = run_geometry(d, plan_geometry(N, plan_variant(d.p)), st, row);
+        if (rc) return rc;
+        plan_note(" ");
+        k.p.data_in_fft = 0;
+    }
+    return run_geometry(k, geom, st, row);
+}
+
+static int run_geometry(KP &k, int geom, hipStream_t st, float *row) {
+    switch (geom) {
         case PSS_PLAN_SINGLE: return run_single(k, st);
         case PSS_PLAN_FOURSTEP: return run_fourstep(k, st, row);
         case PSS_PLAN_SMOOTH: return run_smooth(k, st);
